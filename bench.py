@@ -17,7 +17,13 @@ docs/BENCHMARKS.md) — 10 keeps a margin above the 8-epoch plateau.  The
 per-step best_score is printed so reduced-quality runs are visible.
 
 Run:  python bench.py [--gpus N] [--steps K] [--warmup W]
+                      [--dump-outputs DIR] [--full]
 (N>1 is launched by the driver via torch.distributed.run, one rank/GPU.)
+
+A plain run sets up, warms up, times the K steps and prints the result
+line; that is everything this benchmark measures, so --full (the switch
+for measurements beyond the headline figure) has nothing to add today.
+--dump-outputs DIR saves the last timed step's results as DIR/<name>.npy.
 """
 
 import argparse
@@ -38,6 +44,32 @@ def make_synthetic(n, f, seed=0):
     return X, y
 
 
+def dump_outputs(gs, out_dir, n_folds):
+    """Save what a caller of the timed fit receives, one .npy per array
+    (all float32/float64; a few hundred KB at the flagship size).  The
+    wall-clock columns of cv_results_ are left out: they are measurements,
+    not results."""
+    os.makedirs(out_dir, exist_ok=True)
+    res = gs.cv_results_
+    best = gs.best_estimator_
+    arrays = {
+        "split_test_score": np.stack(
+            [res[f"split{k}_test_score"] for k in range(n_folds)], axis=1),
+        "mean_test_score": res["mean_test_score"],
+        "std_test_score": res["std_test_score"],
+        "rank_test_score": res["rank_test_score"],
+        "best_index": gs.best_index_,
+        "best_score": gs.best_score_,
+        "best_coef": best.coef_,
+        "best_intercept": best.intercept_,
+    }
+    for name, arr in arrays.items():
+        arr = np.asarray(arr)
+        if arr.dtype != np.float32:
+            arr = arr.astype(np.float64)
+        np.save(os.path.join(out_dir, name + ".npy"), arr)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -53,7 +85,19 @@ def main():
                     help="rank 0 saves the last step's mean_test_score "
                          "+ best_index_ to this .npz (dry-run equality "
                          "checks across world sizes)")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="rank 0 saves what the last timed step returned "
+                         "(cv scores, ranks, best index/score, refit "
+                         "coef/intercept) as DIR/<name>.npy, float32 or "
+                         "float64; inputs are seeded, so two builds can be "
+                         "compared output for output")
+    ap.add_argument("--full", action="store_true",
+                    help="also run the measurements beyond the headline "
+                         "figure; this benchmark has none, so the flag "
+                         "changes nothing")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -114,6 +158,8 @@ def main():
             best_index=np.int64(gs.best_index_),
             coef=gs.best_estimator_.coef_,
         )
+    if rank == 0 and args.dump_outputs and gs is not None:
+        dump_outputs(gs, args.dump_outputs, args.folds)
     if rank == 0:
         out = {
             "metric": "candidate-fits/sec",

@@ -50,6 +50,39 @@ def _run_bench(nproc, cand_per_gpu, dump, extra=()):
     return json.loads(line[-1])
 
 
+def test_bench_dump_outputs_and_full(tmp_path):
+    """--dump-outputs writes the last timed step's results as float
+    .npy files that agree with --dump-cv; --full is accepted; the result
+    line reports the steps asked for and their per-step time."""
+    cv = str(tmp_path / "cv.npz")
+    out_dir = tmp_path / "outputs"
+    r = _run_bench(1, 6, cv, extra=("--steps", "2", "--dump-outputs",
+                                    str(out_dir), "--full"))
+    assert r["steps"] == 2
+    assert r["ms_per_step"] > 0
+    assert r["value"] == pytest.approx(
+        r["config"]["fits_per_step"] / (r["ms_per_step"] / 1000.0))
+    got = {p.stem: np.load(p) for p in out_dir.glob("*.npy")}
+    assert set(got) == {
+        "split_test_score", "mean_test_score", "std_test_score",
+        "rank_test_score", "best_index", "best_score", "best_coef",
+        "best_intercept",
+    }
+    for name, arr in got.items():
+        assert arr.dtype in (np.float32, np.float64), (name, arr.dtype)
+        assert np.isfinite(arr).all(), name
+    assert sum(a.nbytes for a in got.values()) <= 64 * 2 ** 20
+    assert got["split_test_score"].shape == (6, r["config"]["folds"])
+    ref = np.load(cv)
+    np.testing.assert_array_equal(
+        got["mean_test_score"], ref["mean_test_score"])
+    np.testing.assert_array_equal(
+        got["split_test_score"].mean(axis=1), ref["mean_test_score"])
+    assert got["best_index"] == ref["best_index"]
+    assert got["best_score"] == r["config"]["best_score"]
+    np.testing.assert_array_equal(got["best_coef"], ref["coef"])
+
+
 @pytest.mark.timeout(900)
 def test_bench_world4_bitwise_matches_world1(tmp_path):
     d1 = str(tmp_path / "w1.npz")

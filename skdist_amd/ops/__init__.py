@@ -46,18 +46,38 @@ def require_hip():
     return _ext
 
 
+GRAM_MAX_BYTES = 768  # csrc/hash_kernels.hip: GRAM_MAX
+CHAR_WB_MAX_CHARS = 32  # csrc/hash_kernels.hip: WIN_CHARS
+
+
+class HashGramOverflow(ValueError):
+    """An n-gram did not fit the UTF-8 hashing kernel's buffer."""
+
+
 def hash_vectorize(docs, n_features=2 ** 20, analyzer="word",
                    ngram_range=(1, 1), alternate_sign=True, binary=False,
                    norm="l2", lowercase=True, dtype="float64",
                    device="cuda"):
     """Device hashing vectorizer: tokenize + murmur3 + CSR, sklearn-exact
-    for ASCII input (kernel: csrc/hash_kernels.hip; reference analog:
-    sklearn HashingVectorizer inside skdist/preprocessing.py:264-310).
+    for any Unicode text under the default ``word`` / ``char_wb``
+    analyzers (kernels: csrc/hash_kernels.hip; reference analog: sklearn
+    HashingVectorizer inside skdist/preprocessing.py:264-310).
 
-    Documents are packed into ONE byte buffer uploaded to HBM; the kernel
-    emits (doc*F + feature, ±1) COO pairs; torch sorts + segment-sums
-    them and the result returns as a scipy CSR (same dtype/norm contract
-    as sklearn's transform).
+    Documents are lowercased on the host (``str.lower()``, so the Unicode
+    case mapping is Python's own), packed into ONE UTF-8 byte buffer and
+    uploaded to HBM.  A pure-ASCII buffer goes to the byte-oriented
+    ``k_hash_vectorize``; any other buffer goes to
+    ``k_hash_vectorize_utf8``, which walks code points with Python's
+    ``\\w`` / ``\\s`` classes (ops/unicode_tables.py).  The kernel emits
+    (doc*F + feature, ±1) COO pairs; torch sorts + segment-sums them and
+    the result returns as a scipy CSR (same dtype/norm contract as
+    sklearn's transform).
+
+    Raises ``UnicodeEncodeError`` for a document that cannot be encoded
+    (lone surrogate) and ``HashGramOverflow`` (a ``ValueError``) when a
+    non-ASCII buffer holds a word n-gram (n >= 2) longer than
+    ``GRAM_MAX_BYTES`` bytes.  Known deviation: on a pure-ASCII buffer
+    such an n-gram is skipped without an error (docs/PARITY.md).
     """
     import numpy as np
     import scipy.sparse as sp
@@ -79,6 +99,15 @@ def hash_vectorize(docs, n_features=2 ** 20, analyzer="word",
     dev = torch.device(device)
     bytes_t = torch.as_tensor(blob, device=dev)
     off_t = torch.as_tensor(off, device=dev)
+    # routing: an all-ASCII buffer keeps the byte-oriented kernel.  One
+    # reduction over the uploaded buffer: the same reduction in numpy
+    # costs ~16 ms per 130 MB on the host, which showed in the ASCII
+    # throughput (profiles/r03_hash_unicode.txt)
+    utf8 = bool(len(blob)) and int(bytes_t.max().item()) >= 0x80
+    if utf8:
+        from .unicode_tables import device_tables
+
+        word_tbl, ws_list = device_tables(bytes_t.device)
     orders = max_n - min_n + 1
     if mode == 0:
         cap = int(len(blob) // 3 + n_docs + 64) * orders
@@ -87,11 +116,24 @@ def hash_vectorize(docs, n_features=2 ** 20, analyzer="word",
     while True:
         keys = torch.empty(max(cap, 64), dtype=torch.int64, device=dev)
         vals = torch.empty(max(cap, 64), dtype=torch.float32, device=dev)
-        ctr = torch.zeros(1, dtype=torch.int64, device=dev)
-        ext.hash_vectorize(bytes_t, off_t, mode, min_n, max_n,
-                           n_features, int(alternate_sign), keys, vals,
-                           ctr)
-        total = int(ctr.item())
+        # ctr[0]: pairs emitted; ctr[1]: overflow flag (UTF-8 kernel only)
+        ctr = torch.zeros(2, dtype=torch.int64, device=dev)
+        if utf8:
+            ext.hash_vectorize_utf8(bytes_t, off_t, mode, min_n, max_n,
+                                    n_features, int(alternate_sign),
+                                    word_tbl, ws_list, keys, vals, ctr)
+        else:
+            ext.hash_vectorize(bytes_t, off_t, mode, min_n, max_n,
+                               n_features, int(alternate_sign), keys,
+                               vals, ctr)
+        total, overflow = ctr.tolist()
+        if overflow:
+            raise HashGramOverflow(
+                "hash_vectorize: an n-gram does not fit the kernel's "
+                f"buffer (word n-grams with n >= 2: {GRAM_MAX_BYTES} "
+                f"bytes; char_wb: {CHAR_WB_MAX_CHARS} characters); "
+                "use sklearn's HashingVectorizer for these documents"
+            )
         if total <= cap:
             break
         cap = total  # exact size known now; one retry

@@ -427,6 +427,11 @@ extern "C" hipError_t skdist_hash_vectorize(
     const void* bytes, const void* doc_off, long long n_docs, int mode,
     int min_n, int max_n, int n_features, int alt_sign, void* out_keys,
     void* out_vals, void* ctr, long long cap, hipStream_t stream);
+extern "C" hipError_t skdist_hash_vectorize_utf8(
+    const void* bytes, const void* doc_off, long long n_docs, int mode,
+    int min_n, int max_n, int n_features, int alt_sign,
+    const void* word_tbl, const void* ws_list, int n_ws, void* out_keys,
+    void* out_vals, void* ctr, long long cap, hipStream_t stream);
 
 namespace {
 
@@ -583,6 +588,49 @@ void hash_vectorize(torch::Tensor bytes, torch::Tensor doc_off,
                 hipGetErrorString(err));
 }
 
+// UTF-8 tokenizer: word_tbl is the \w bitmap over U+0000..U+10FFFF
+// (0x110000/32 int32 words), ws_list the sorted \s code points, and ctr
+// holds {pair count, overflow flag}.
+void hash_vectorize_utf8(torch::Tensor bytes, torch::Tensor doc_off,
+                         int64_t mode, int64_t min_n, int64_t max_n,
+                         int64_t n_features, int64_t alt_sign,
+                         torch::Tensor word_tbl, torch::Tensor ws_list,
+                         torch::Tensor out_keys, torch::Tensor out_vals,
+                         torch::Tensor ctr) {
+    for (auto* t : {&bytes, &doc_off, &word_tbl, &ws_list, &out_keys,
+                    &out_vals, &ctr}) {
+        CHECK_DEV(*t);
+        CHECK_CONT(*t);
+    }
+    TORCH_CHECK(bytes.scalar_type() == torch::kUInt8, "bytes must be u8");
+    TORCH_CHECK(doc_off.scalar_type() == torch::kInt64 &&
+                    doc_off.numel() >= 1,
+                "doc_off must be int64 [n_docs + 1]");
+    TORCH_CHECK(word_tbl.scalar_type() == torch::kInt32 &&
+                    word_tbl.numel() == 0x110000 / 32,
+                "word_tbl must be int32 [0x110000 / 32]");
+    TORCH_CHECK(ws_list.scalar_type() == torch::kInt32 &&
+                    ws_list.numel() <= 64,
+                "ws_list must be int32 with at most 64 entries");
+    TORCH_CHECK(ctr.scalar_type() == torch::kInt64 && ctr.numel() >= 2,
+                "ctr must be int64 [2]: {count, overflow}");
+    TORCH_CHECK(out_vals.numel() >= out_keys.numel(),
+                "out_vals shorter than out_keys");
+    TORCH_CHECK(mode == 0 || mode == 1, "mode must be 0 or 1");
+    TORCH_CHECK(min_n >= 1 && max_n <= (mode == 0 ? 8 : 32),
+                "ngram_range outside the kernel's limits "
+                "(word: 1..8 tokens, char_wb: 1..32 characters)");
+    auto stream = c10::hip::getCurrentHIPStream().stream();
+    hipError_t err = skdist_hash_vectorize_utf8(
+        bytes.data_ptr(), doc_off.data_ptr(), doc_off.size(0) - 1,
+        (int)mode, (int)min_n, (int)max_n, (int)n_features, (int)alt_sign,
+        word_tbl.data_ptr(), ws_list.data_ptr(), (int)ws_list.numel(),
+        out_keys.data_ptr(), out_vals.data_ptr(), ctr.data_ptr(),
+        out_keys.size(0), stream);
+    TORCH_CHECK(err == hipSuccess, "hash_vectorize_utf8: ",
+                hipGetErrorString(err));
+}
+
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
@@ -602,6 +650,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "fused standardize + augment + bf16 cast");
     m.def("hash_vectorize", &hash_vectorize,
           "tokenize + murmur3 feature hashing -> COO pairs");
+    m.def("hash_vectorize_utf8", &hash_vectorize_utf8,
+          "UTF-8 tokenize + murmur3 feature hashing -> COO pairs");
     m.def("tree_hist", &tree_hist, "per-(node,feature,bin) stats");
     m.def("tree_split", &tree_split, "best split per frontier node");
     m.def("part_count", &part_count, "partition phase A: left counts");

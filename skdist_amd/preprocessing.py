@@ -13,7 +13,9 @@ import pandas as pd
 import scipy.sparse as sparse
 from sklearn import feature_selection
 from sklearn.base import BaseEstimator, TransformerMixin, clone
-from sklearn.feature_extraction.text import HashingVectorizer
+from sklearn.feature_extraction.text import (
+    HashingVectorizer, strip_accents_ascii, strip_accents_unicode,
+)
 from sklearn.preprocessing import LabelEncoder, MultiLabelBinarizer, normalize
 
 __all__ = [
@@ -182,10 +184,16 @@ class HashingVectorizerChunked(HashingVectorizer):
 
     def _try_device_transform(self, docs):
         """HIP fast path (ops/csrc/hash_kernels.hip): tokenize + murmur3 +
-        CSR on the GPU, bit-exact with sklearn for ASCII docs under the
-        default word / char_wb analyzers; anything else (custom
-        tokenizers, stop words, non-ASCII) keeps the sklearn path."""
-        from .ops import hash_vectorize, hip_available
+        CSR on the GPU, bit-exact with sklearn for any Unicode text under
+        the default word / char_wb analyzers, with ``strip_accents`` None,
+        "ascii" or "unicode" (applied on the host after lowercasing,
+        sklearn's own order).  Returns None, so the chunk keeps the
+        sklearn path, for anything else: a custom token_pattern,
+        tokenizer, preprocessor or callable strip_accents, stop words,
+        non-content input, n-gram limits (word > 8, char_wb > 32),
+        non-str documents, a document that cannot be encoded as UTF-8
+        (lone surrogate), or a word n-gram too long for the kernel."""
+        from .ops import HashGramOverflow, hash_vectorize, hip_available
 
         if not hip_available():
             return None
@@ -201,17 +209,38 @@ class HashingVectorizerChunked(HashingVectorizer):
             return None
         if (self.stop_words is not None or self.preprocessor is not None
                 or self.tokenizer is not None
-                or self.strip_accents is not None
                 or self.input != "content"):
             return None
-        if not all(isinstance(d, str) and d.isascii() for d in docs):
+        if self.strip_accents is None:
+            strip = None
+        elif self.strip_accents == "ascii":
+            strip = strip_accents_ascii
+        elif self.strip_accents == "unicode":
+            strip = strip_accents_unicode
+        else:
             return None
-        return hash_vectorize(
-            docs, n_features=self.n_features, analyzer=self.analyzer,
-            ngram_range=self.ngram_range,
-            alternate_sign=self.alternate_sign, binary=self.binary,
-            norm=self.norm, lowercase=self.lowercase, dtype=self.dtype,
-        )
+        if not all(isinstance(d, str) for d in docs):
+            return None
+        lowercase = self.lowercase
+        if strip is not None:
+            # sklearn's preprocessing order: lower(), then strip accents
+            if lowercase:
+                docs = [strip(d.lower()) for d in docs]
+                lowercase = False
+            else:
+                docs = [strip(d) for d in docs]
+        try:
+            return hash_vectorize(
+                docs, n_features=self.n_features, analyzer=self.analyzer,
+                ngram_range=self.ngram_range,
+                alternate_sign=self.alternate_sign, binary=self.binary,
+                norm=self.norm, lowercase=lowercase, dtype=self.dtype,
+            )
+        except (UnicodeEncodeError, HashGramOverflow):
+            # a lone surrogate cannot be packed as UTF-8 (hash_vectorize
+            # raises while encoding, before anything reaches the device);
+            # an over-long n-gram is refused by the kernel
+            return None
 
 
 class MultihotEncoder(TransformerMixin, BaseEstimator):

@@ -43,7 +43,7 @@ import torch
 from sklearn.base import BaseEstimator, ClassifierMixin, RegressorMixin
 
 from ._sgd import as_dense_f32
-from .forest import BinnedDataset, ForestBuilder, HistTree
+from .forest import BinnedDataset, ForestBuilder, HistTree, canonical_csr
 
 
 def _leaf_rows(tree, X):
@@ -58,6 +58,8 @@ def _leaf_value_rows(tree, X, Xdev, dev):
     if Xdev is None:
         return torch.as_tensor(_leaf_rows(tree, X), dtype=torch.int64,
                                device=dev)
+    csr = isinstance(Xdev, tuple)   # resident (indptr, indices, data)
+    n = len(Xdev[0]) - 1 if csr else len(Xdev)
     from ..ops import require_hip
 
     ext = require_hip()
@@ -68,8 +70,11 @@ def _leaf_value_rows(tree, X, Xdev, dev):
     left = as_t(tree.left, torch.int32)
     right = as_t(tree.right, torch.int32)
     roots = torch.zeros(1, dtype=torch.int32, device=dev)
-    out = torch.empty(len(Xdev), 1, dtype=torch.int32, device=dev)
-    ext.forest_apply(Xdev, feat, thr, left, right, roots, out)
+    out = torch.empty(n, 1, dtype=torch.int32, device=dev)
+    if csr:
+        ext.forest_apply_csr(*Xdev, feat, thr, left, right, roots, out)
+    else:
+        ext.forest_apply(Xdev, feat, thr, left, right, roots, out)
     return left.index_select(
         0, out[:, 0].to(torch.int64)).to(torch.int64)
 
@@ -125,7 +130,14 @@ class _BaseHistGB(BaseEstimator):
             raise NotImplementedError(
                 "sample_weight is not supported by the hist-GBT yet"
             )
-        X = as_dense_f32(X)
+        import scipy.sparse as sp
+
+        sparse = sp.issparse(X)
+        if sparse:
+            # binned, traversed and kept resident as CSR; never densified
+            X = canonical_csr(X)
+        else:
+            X = as_dense_f32(X)
         n = X.shape[0]
         sc = getattr(self, "sc", None)
         device = (
@@ -179,7 +191,11 @@ class _BaseHistGB(BaseEstimator):
         Ft = torch.as_tensor(F, dtype=torch.float64, device=dev)
         self._to_device_targets(dev)
         Xdev = None
-        if dev.type == "cuda":
+        if dev.type == "cuda" and sparse:
+            Xdev = tuple(
+                torch.as_tensor(a, device=dev)
+                for a in (X.indptr, X.indices, X.data))
+        elif dev.type == "cuda":
             Xdev = torch.as_tensor(
                 np.ascontiguousarray(X), device=dev)
         val_t = (
@@ -266,8 +282,9 @@ class _BaseHistGB(BaseEstimator):
                 "Call 'fit' before using this estimator.")
 
         if sp.issparse(X):
-            X = X.toarray()
-        X = np.asarray(X, dtype=np.float32)
+            X = canonical_csr(X, self.n_features_in_)
+        else:
+            X = np.asarray(X, dtype=np.float32)
         K = len(self.stages_[0])
         out = np.tile(self._base_raw(), (X.shape[0], 1))
         for round_trees in self.stages_:
@@ -283,8 +300,9 @@ class _BaseHistGB(BaseEstimator):
         import scipy.sparse as sp
 
         if sp.issparse(X):
-            X = X.toarray()
-        X = np.asarray(X, dtype=np.float32)
+            X = canonical_csr(X, self.n_features_in_)
+        else:
+            X = np.asarray(X, dtype=np.float32)
         out = np.tile(self._base_raw(), (X.shape[0], 1))
         for round_trees in self.stages_:
             for k, tree in enumerate(round_trees):

@@ -111,19 +111,28 @@ class HistTree:
         return len(self.feature)
 
     def apply(self, X):
-        """Leaf NODE index per row (vectorized host traversal)."""
+        """Leaf NODE index per row (vectorized host traversal).
+
+        A scipy-sparse X is read cell by cell through CSR paired
+        indexing (absent cell = 0.0); it is never densified."""
         import scipy.sparse as sp
 
-        if sp.issparse(X):
-            X = X.toarray()
-        X = np.asarray(X, dtype=np.float32)
-        node = np.zeros(len(X), dtype=np.int64)
+        sparse = sp.issparse(X)
+        if sparse:
+            X = X.tocsr()
+        else:
+            X = np.asarray(X, dtype=np.float32)
+        node = np.zeros(X.shape[0], dtype=np.int64)
         active = self.feature[node] >= 0
         while active.any():
             idx = np.flatnonzero(active)
             nd = node[idx]
             f = self.feature[nd]
-            go_left = X[idx, f] <= self.threshold[nd]
+            if sparse:
+                xv = np.asarray(X[idx, f]).ravel().astype(np.float32)
+            else:
+                xv = X[idx, f]
+            go_left = xv <= self.threshold[nd]
             node[idx] = np.where(go_left, self.left[nd], self.right[nd])
             active[idx] = self.feature[node[idx]] >= 0
         return node
@@ -146,12 +155,205 @@ class HistTree:
 # binned dataset (built once per forest fit, shared by every tree)
 # --------------------------------------------------------------------- #
 
+def canonical_csr(X, n_features=None):
+    """Canonical CSR COPY of a scipy-sparse X for the sparse tree kernels
+    (k_bin_csr, k_forest_predict_csr / k_forest_apply_csr): float32 data,
+    duplicates summed, indices sorted, int32 column indices, int64 indptr.
+    The caller's matrix is never mutated.  Raises before any launch on a
+    malformed ``indptr``, a column index outside ``[0, f)`` or a width
+    other than ``n_features``."""
+    import scipy.sparse as sp
+
+    n, f = X.shape
+    if n_features is not None and f != n_features:
+        raise ValueError(
+            f"X has {f} features, but the model was fitted with "
+            f"{n_features}")
+    if f >= 2 ** 31:
+        raise ValueError("sparse X wider than 2^31-1 columns")
+    A = X.tocsr() if not sp.isspmatrix_csr(X) else X
+    # duplicates are summed in X's own dtype and cast afterwards, the
+    # order toarray() followed by a float32 cast uses
+    data = np.array(A.data, copy=True)
+    indices = np.array(A.indices, dtype=np.int64, copy=True)
+    indptr = np.array(A.indptr, dtype=np.int64, copy=True)
+    if (len(indptr) != n + 1 or indptr[0] != 0
+            or indptr[-1] != len(indices) or len(indices) != len(data)
+            or (n and np.any(np.diff(indptr) < 0))):
+        raise ValueError("sparse X has an inconsistent indptr")
+    if len(indices) and (indices.min() < 0 or indices.max() >= f):
+        raise ValueError(
+            f"sparse X holds a column index outside [0, {f})")
+    C = sp.csr_matrix((data, indices.astype(np.int32), indptr),
+                      shape=(n, f))
+    C.sum_duplicates()
+    C.sort_indices()
+    C.indices = np.ascontiguousarray(C.indices, dtype=np.int32)
+    C.indptr = np.ascontiguousarray(C.indptr, dtype=np.int64)
+    C.data = np.ascontiguousarray(C.data, dtype=np.float32)
+    return C
+
+
+def _sparse_quantile_edges(C, nbins, device):
+    """``torch.quantile(C.toarray(), qs, dim=0).t()`` without the dense
+    matrix: [f, nbins-1] float32, bit-identical to the dense result.
+
+    The order statistics of a virtual dense column are its sorted
+    negatives, then (rows - nnz_col) zeros, then its sorted positives.
+    torch.quantile reads ranks floor/ceil(q·(rows-1)) and joins them with
+    ``lerp(lo, hi, q·(rows-1) - floor)``; the same float32 rank
+    arithmetic runs here on the same device, the two order statistics are
+    gathered from the per-column sorted nonzeros, and ``torch.lerp``
+    joins them."""
+    ns, f = C.shape
+    qs = torch.linspace(0, 1, nbins + 1, device=device)[1:-1]
+    ranks = qs * (ns - 1)
+    r_lo = ranks.floor().to(torch.int64)
+    w = ranks - r_lo
+    r_hi = ranks.ceil().to(torch.int64).cpu().numpy()
+    r_lo = r_lo.cpu().numpy()
+
+    # stored nonzeros, sorted by (column, value)
+    nz = C.data != 0
+    cols = C.indices[nz].astype(np.int64)
+    vals = C.data[nz]
+    order = np.lexsort((vals, cols))
+    cols = cols[order]
+    vals = vals[order]
+    colptr = np.zeros(f + 1, dtype=np.int64)
+    np.cumsum(np.bincount(cols, minlength=f), out=colptr[1:])
+    n_neg = np.bincount(cols[vals < 0], minlength=f).astype(np.int64)
+    n_zero = ns - (colptr[1:] - colptr[:-1])    # implicit + stored zeros
+    # one trailing pad so masked-out gathers stay in range
+    vals = np.concatenate([vals, np.zeros(1, dtype=np.float32)])
+
+    def order_stat(r, j0, j1):
+        # r: [nq] ranks; columns j0:j1 → [j1-j0, nq] float32
+        neg = n_neg[j0:j1, None]
+        zero = n_zero[j0:j1, None]
+        base = colptr[j0:j1, None]
+        rr = r[None, :]
+        in_neg = rr < neg
+        in_pos = rr >= neg + zero
+        pos = np.where(in_neg, base + rr, base + rr - zero)
+        pos = np.where(in_neg | in_pos, pos, len(vals) - 1)
+        return vals[pos]
+
+    edges = torch.empty(f, nbins - 1, dtype=torch.float32, device=device)
+    step = max(1, (1 << 24) // max(nbins - 1, 1))
+    for j0 in range(0, f, step):
+        j1 = min(f, j0 + step)
+        lo = torch.as_tensor(order_stat(r_lo, j0, j1), device=device)
+        hi = torch.as_tensor(order_stat(r_hi, j0, j1), device=device)
+        edges[j0:j1] = torch.lerp(lo, hi, w.unsqueeze(0))
+    return edges
+
+
+def _csr_row_chunks(indptr, max_rows, max_nnz):
+    """Row ranges [lo, hi) holding at most ``max_rows`` rows and, unless
+    a single row is larger, at most ``max_nnz`` stored entries."""
+    n = len(indptr) - 1
+    lo = 0
+    while lo < n:
+        hi = int(np.searchsorted(indptr, indptr[lo] + max_nnz,
+                                 side="right")) - 1
+        hi = min(max(hi, lo + 1), lo + max_rows, n)
+        yield lo, hi
+        lo = hi
+
+
+def _bin_csr_eager(indptr, indices, data, edges, zc, n):
+    """Torch mirror of k_bin_csr (CPU tier / SKDIST_AMD_ALLOW_EAGER):
+    every row starts as the zero-code pattern, then each stored entry is
+    overwritten with the number of its feature's edges strictly below
+    its value."""
+    codes = zc.unsqueeze(0).repeat(n, 1).contiguous()
+    nnz = len(data)
+    if nnz == 0:
+        return codes
+    rows = torch.repeat_interleave(
+        torch.arange(n, device=data.device), indptr[1:] - indptr[:-1])
+    cols = indices.to(torch.int64)
+    step = max(1, (1 << 24) // max(edges.shape[1], 1))
+    for k0 in range(0, nnz, step):
+        sl = slice(k0, k0 + step)
+        c = (edges[cols[sl]] < data[sl].unsqueeze(1)).sum(dim=1)
+        codes[rows[sl], cols[sl]] = c.to(torch.uint8)
+    return codes
+
+
 class BinnedDataset:
-    """Quantile-binned (X, y) resident on one device."""
+    """Quantile-binned (X, y) resident on one device.
+
+    A scipy-sparse X is binned from its CSR arrays (k_bin_csr on GPU, a
+    torch mirror on CPU) into the same ``edges`` and ``codes`` the dense
+    constructor computes for ``X.toarray()``; only the uint8 code matrix
+    is dense."""
 
     def __init__(self, X, y, device, is_cls, classes=None, nbins=256,
                  max_bin_sample=200_000, seed=0):
+        import scipy.sparse as sp
+
         self.device = torch.device(device)
+        if sp.issparse(X):
+            self._init_codes_csr(X, nbins, max_bin_sample, seed)
+        else:
+            self._init_codes_dense(X, nbins, max_bin_sample, seed)
+        self._init_targets(y, is_cls, classes)
+
+    def _init_codes_csr(self, X, nbins, max_bin_sample, seed):
+        import os
+
+        from ._sgd import check_finite
+
+        self.n, self.f = X.shape
+        self.nbins = nbins
+        self.fp = (self.f + 3) // 4 * 4
+        gb = self.n * self.fp / 1e9
+        limit = float(os.environ.get("SKDIST_AMD_DENSIFY_GB", "64"))
+        if gb > limit:
+            raise ValueError(
+                f"the uint8 code matrix of sparse X ({self.n} x {self.fp}) "
+                f"would take {gb:.1f} GB (> {limit:.0f} GB; set "
+                "SKDIST_AMD_DENSIFY_GB to raise the limit)")
+        C = canonical_csr(X)
+        check_finite(torch.from_numpy(C.data), "X")
+        dev = self.device
+
+        if self.n > max_bin_sample:
+            g = torch.Generator(device="cpu")
+            g.manual_seed(seed)
+            sub = torch.randperm(self.n, generator=g)[:max_bin_sample]
+            Cs = C[sub.numpy()]
+        else:
+            Cs = C
+        self.edges = _sparse_quantile_edges(Cs, nbins, dev)
+        del Cs
+
+        # a cell with no stored entry holds 0.0: its code is the number
+        # of edges strictly below zero; pad columns stay 0
+        zc = torch.zeros(self.fp, dtype=torch.uint8, device=dev)
+        zc[: self.f] = (self.edges < 0).sum(dim=1).to(torch.uint8)
+        indptr = torch.as_tensor(C.indptr, device=dev)
+        indices = torch.as_tensor(C.indices, device=dev)
+        data = torch.as_tensor(C.data, device=dev)
+        use_hip = dev.type == "cuda"
+        if use_hip and _allow_eager():
+            from ..ops import hip_available
+
+            use_hip = hip_available()
+        if use_hip:
+            from ..ops import require_hip
+
+            self.codes = torch.empty(self.n, self.fp, dtype=torch.uint8,
+                                     device=dev)
+            require_hip().bin_csr(indptr, indices, data, self.edges, zc,
+                                  self.codes, self.f)
+        else:
+            self.codes = _bin_csr_eager(indptr, indices, data, self.edges,
+                                        zc, self.n)
+
+    def _init_codes_dense(self, X, nbins, max_bin_sample, seed):
         X = np.ascontiguousarray(X, dtype=np.float32)
         self.n, self.f = X.shape
         self.nbins = nbins
@@ -184,6 +386,7 @@ class BinnedDataset:
         self.codes = self.codes.contiguous()
         del XT, Xt, Xs, codes_fm
 
+    def _init_targets(self, y, is_cls, classes):
         self.is_cls = is_cls
         if is_cls:
             y_np = np.asarray(y)
@@ -1031,7 +1234,7 @@ class FlatForest:
         import scipy.sparse as sp
 
         if sp.issparse(X):
-            X = X.toarray()
+            return self._predict_value_csr(X, chunk_rows)
         X = np.ascontiguousarray(X, dtype=np.float32)
         outs = []
         for lo in range(0, len(X), chunk_rows):
@@ -1043,6 +1246,49 @@ class FlatForest:
                                      self.right, self.roots, self.values,
                                      out)
             outs.append(out.cpu().numpy())
+        return np.concatenate(outs, axis=0)
+
+    # stored entries uploaded per CSR chunk (12 bytes each on device)
+    CSR_CHUNK_NNZ = 1 << 27
+
+    def _csr_chunks(self, X, chunk_rows):
+        """Canonicalise a scipy-sparse X and yield per-chunk device
+        ``(rows, indptr, indices, data)`` with ``indptr`` rebased to 0.
+        Chunks are bounded by a row count and a stored-entry count; X is
+        never densified."""
+        C = canonical_csr(X, self.n_features)
+        for lo, hi in _csr_row_chunks(C.indptr, chunk_rows,
+                                      self.CSR_CHUNK_NNZ):
+            a, b = int(C.indptr[lo]), int(C.indptr[hi])
+            dev = self.device
+            yield (
+                hi - lo,
+                torch.as_tensor(C.indptr[lo: hi + 1] - a, device=dev),
+                torch.as_tensor(C.indices[a:b], device=dev),
+                torch.as_tensor(C.data[a:b], device=dev),
+            )
+
+    def _predict_value_csr(self, X, chunk_rows):
+        outs = [np.zeros((0, self.vs), dtype=np.float32)]
+        for rows, indptr, indices, data in self._csr_chunks(X, chunk_rows):
+            out = torch.empty(rows, self.vs, dtype=torch.float32,
+                              device=self.device)
+            self._ext.forest_predict_csr(
+                indptr, indices, data, self.feat, self.thr, self.left,
+                self.right, self.roots, self.values, out)
+            outs.append(out.cpu().numpy())
+        return np.concatenate(outs, axis=0)
+
+    def _apply_csr(self, X, chunk_rows):
+        roots_np = self.roots.cpu().numpy().astype(np.int64)
+        outs = [np.zeros((0, self.n_trees), dtype=np.int64)]
+        for rows, indptr, indices, data in self._csr_chunks(X, chunk_rows):
+            out = torch.empty(rows, self.n_trees, dtype=torch.int32,
+                              device=self.device)
+            self._ext.forest_apply_csr(
+                indptr, indices, data, self.feat, self.thr, self.left,
+                self.right, self.roots, out)
+            outs.append(out.cpu().numpy() - roots_np[None, :])
         return np.concatenate(outs, axis=0)
 
     def predict_proba(self, X):
@@ -1060,7 +1306,7 @@ class FlatForest:
         import scipy.sparse as sp
 
         if sp.issparse(X):
-            X = X.toarray()
+            return self._apply_csr(X, chunk_rows)
         X = np.ascontiguousarray(X, dtype=np.float32)
         roots_np = self.roots.cpu().numpy().astype(np.int64)
         outs = []

@@ -416,6 +416,20 @@ extern "C" hipError_t skdist_forest_apply(
     const void* X, const void* feat, const void* thr, const void* left,
     const void* right, const void* roots, void* out_leaf, long long rows,
     int f, int n_trees, hipStream_t stream);
+extern "C" hipError_t skdist_forest_predict_csr(
+    const void* indptr, const void* indices, const void* data,
+    const void* feat, const void* thr, const void* left, const void* right,
+    const void* roots, const void* values, void* out, long long rows,
+    long long nnz, int n_trees, int vs, hipStream_t stream);
+extern "C" hipError_t skdist_forest_apply_csr(
+    const void* indptr, const void* indices, const void* data,
+    const void* feat, const void* thr, const void* left, const void* right,
+    const void* roots, void* out_leaf, long long rows, long long nnz,
+    int n_trees, hipStream_t stream);
+extern "C" hipError_t skdist_bin_csr(
+    const void* indptr, const void* indices, const void* data,
+    const void* edges, const void* zc4, void* codes, long long n,
+    long long nnz, int f, int fp, int nedges, hipStream_t stream);
 extern "C" hipError_t skdist_score(
     const void* Xf, const void* WbfT, const void* yf, void* out,
     long long m_pad, int fa, int ncols_pad, int mode,
@@ -534,6 +548,125 @@ void forest_apply(torch::Tensor X, torch::Tensor feat, torch::Tensor thr,
         (int)X.size(1), (int)roots.size(0), stream);
     TORCH_CHECK(err == hipSuccess, "forest_apply: ",
                 hipGetErrorString(err));
+}
+
+// CSR inputs shared by the sparse tree kernels: indptr int64 [rows+1],
+// indices int32 [nnz], data f32 [nnz], all contiguous on the GPU
+void check_csr(const torch::Tensor& indptr, const torch::Tensor& indices,
+               const torch::Tensor& data, int64_t rows) {
+    for (auto* t : {&indptr, &indices, &data}) {
+        CHECK_DEV(*t);
+        CHECK_CONT(*t);
+        TORCH_CHECK(t->dim() == 1, "CSR arrays must be 1-D");
+    }
+    TORCH_CHECK(indptr.scalar_type() == torch::kInt64,
+                "indptr must be int64");
+    TORCH_CHECK(indices.scalar_type() == torch::kInt32,
+                "indices must be int32");
+    TORCH_CHECK(data.scalar_type() == torch::kFloat32, "data must be f32");
+    TORCH_CHECK(rows >= 0 && indptr.numel() == rows + 1,
+                "indptr must hold rows+1 offsets");
+    TORCH_CHECK(indices.numel() == data.numel(),
+                "indices and data differ in length");
+}
+
+// node arrays of a flattened forest: int32 / f32, equal lengths
+void check_nodes(const torch::Tensor& feat, const torch::Tensor& thr,
+                 const torch::Tensor& left, const torch::Tensor& right,
+                 const torch::Tensor& roots) {
+    for (auto* t : {&feat, &thr, &left, &right, &roots}) {
+        CHECK_DEV(*t);
+        CHECK_CONT(*t);
+    }
+    for (auto* t : {&feat, &left, &right, &roots})
+        TORCH_CHECK(t->scalar_type() == torch::kInt32,
+                    "feat/left/right/roots must be int32");
+    TORCH_CHECK(thr.scalar_type() == torch::kFloat32, "thr must be f32");
+    TORCH_CHECK(thr.numel() == feat.numel() &&
+                    left.numel() == feat.numel() &&
+                    right.numel() == feat.numel(),
+                "node arrays differ in length");
+    TORCH_CHECK(roots.numel() >= 1 && feat.numel() >= 1, "empty forest");
+}
+
+void forest_predict_csr(torch::Tensor indptr, torch::Tensor indices,
+                        torch::Tensor data, torch::Tensor feat,
+                        torch::Tensor thr, torch::Tensor left,
+                        torch::Tensor right, torch::Tensor roots,
+                        torch::Tensor values, torch::Tensor out) {
+    const int64_t rows = out.dim() == 2 ? out.size(0) : -1;
+    check_csr(indptr, indices, data, rows);
+    check_nodes(feat, thr, left, right, roots);
+    for (auto* t : {&values, &out}) {
+        CHECK_DEV(*t);
+        CHECK_CONT(*t);
+        TORCH_CHECK(t->scalar_type() == torch::kFloat32 && t->dim() == 2,
+                    "values/out must be 2-D f32");
+    }
+    const int64_t vs = values.size(1);
+    TORCH_CHECK(vs >= 1 && vs <= 32,
+                "forest_predict_csr carries <= 32 payload values (MAXVS)");
+    TORCH_CHECK(out.size(1) == vs, "out must be [rows, vs]");
+    auto stream = c10::hip::getCurrentHIPStream().stream();
+    hipError_t err = skdist_forest_predict_csr(
+        indptr.data_ptr(), indices.data_ptr(), data.data_ptr(),
+        feat.data_ptr(), thr.data_ptr(), left.data_ptr(),
+        right.data_ptr(), roots.data_ptr(), values.data_ptr(),
+        out.data_ptr(), rows, indices.numel(), (int)roots.numel(),
+        (int)vs, stream);
+    TORCH_CHECK(err == hipSuccess, "forest_predict_csr: ",
+                hipGetErrorString(err));
+}
+
+void forest_apply_csr(torch::Tensor indptr, torch::Tensor indices,
+                      torch::Tensor data, torch::Tensor feat,
+                      torch::Tensor thr, torch::Tensor left,
+                      torch::Tensor right, torch::Tensor roots,
+                      torch::Tensor out_leaf) {
+    const int64_t rows = out_leaf.dim() == 2 ? out_leaf.size(0) : -1;
+    check_csr(indptr, indices, data, rows);
+    check_nodes(feat, thr, left, right, roots);
+    CHECK_DEV(out_leaf);
+    CHECK_CONT(out_leaf);
+    TORCH_CHECK(out_leaf.scalar_type() == torch::kInt32,
+                "out_leaf must be int32");
+    TORCH_CHECK(out_leaf.size(1) == roots.numel(),
+                "out_leaf must be [rows, n_trees]");
+    auto stream = c10::hip::getCurrentHIPStream().stream();
+    hipError_t err = skdist_forest_apply_csr(
+        indptr.data_ptr(), indices.data_ptr(), data.data_ptr(),
+        feat.data_ptr(), thr.data_ptr(), left.data_ptr(),
+        right.data_ptr(), roots.data_ptr(), out_leaf.data_ptr(), rows,
+        indices.numel(), (int)roots.numel(), stream);
+    TORCH_CHECK(err == hipSuccess, "forest_apply_csr: ",
+                hipGetErrorString(err));
+}
+
+void bin_csr(torch::Tensor indptr, torch::Tensor indices,
+             torch::Tensor data, torch::Tensor edges, torch::Tensor zc,
+             torch::Tensor codes, int64_t f) {
+    TORCH_CHECK(codes.dim() == 2, "codes must be [n, fp]");
+    const int64_t n = codes.size(0), fp = codes.size(1);
+    check_csr(indptr, indices, data, n);
+    for (auto* t : {&edges, &zc, &codes}) {
+        CHECK_DEV(*t);
+        CHECK_CONT(*t);
+    }
+    TORCH_CHECK(codes.scalar_type() == torch::kUInt8, "codes must be u8");
+    TORCH_CHECK(zc.scalar_type() == torch::kUInt8 && zc.numel() == fp,
+                "zc must be u8 [fp]");
+    TORCH_CHECK(fp % 4 == 0 && f >= 1 && f <= fp && fp < (1LL << 31),
+                "fp must be f padded to a multiple of 4");
+    TORCH_CHECK(edges.scalar_type() == torch::kFloat32 &&
+                    edges.dim() == 2 && edges.size(0) == f &&
+                    edges.size(1) <= 255,
+                "edges must be f32 [f, nbins-1] with nbins <= 256");
+    auto stream = c10::hip::getCurrentHIPStream().stream();
+    hipError_t err = skdist_bin_csr(
+        indptr.data_ptr(), indices.data_ptr(), data.data_ptr(),
+        edges.data_ptr(), zc.data_ptr(), codes.data_ptr(), n,
+        indices.numel(), (int)f, (int)fp, (int)edges.size(1), stream);
+    TORCH_CHECK(err == hipSuccess, "bin_csr: ", hipGetErrorString(err));
 }
 
 void score_fold(torch::Tensor Xf, torch::Tensor WbfT, torch::Tensor yf,
@@ -658,4 +791,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("part_scatter", &part_scatter, "partition phase B: scatter");
     m.def("forest_predict", &forest_predict, "batched forest inference");
     m.def("forest_apply", &forest_apply, "leaf ids per (row, tree)");
+    m.def("forest_predict_csr", &forest_predict_csr,
+          "batched forest inference over CSR rows");
+    m.def("forest_apply_csr", &forest_apply_csr,
+          "leaf ids per (row, tree) over CSR rows");
+    m.def("bin_csr", &bin_csr, "CSR -> uint8 quantile codes");
 }

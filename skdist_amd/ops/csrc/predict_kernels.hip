@@ -93,3 +93,122 @@ extern "C" hipError_t skdist_forest_apply(
                        (int*)out_leaf, rows, f, n_trees);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------- //
+// CSR rows (scipy-sparse X, never densified)
+//
+//   indptr  [rows+1] int64   (rebased so indptr[0] == 0 for the chunk)
+//   indices [nnz]    int32   ascending within each row, no duplicates
+//   data    [nnz]    f32
+//
+// Same walk as the dense kernels with x[jf] replaced by a binary search of
+// the row's index range: the stored value when column jf is present, 0.0f
+// otherwise.  One thread per row and trees in order t = 0..T-1, so the
+// accumulation order — and therefore every output bit — equals the dense
+// kernel on X.toarray().  Any nnz per row from 0 to f takes this one path.
+// ---------------------------------------------------------------------- //
+static __device__ __forceinline__ float csr_lookup(
+    const int* __restrict__ indices, const float* __restrict__ data,
+    long long lo, long long hi, int jf) {
+    while (lo < hi) {
+        const long long mid = lo + ((hi - lo) >> 1);
+        const int c = indices[mid];
+        if (c < jf) lo = mid + 1;
+        else if (c > jf) hi = mid;
+        else return data[mid];
+    }
+    return 0.f;
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_forest_predict_csr(
+    const long long* __restrict__ indptr, const int* __restrict__ indices,
+    const float* __restrict__ data, const int* __restrict__ feat,
+    const float* __restrict__ thr, const int* __restrict__ left,
+    const int* __restrict__ right, const int* __restrict__ roots,
+    const float* __restrict__ values, float* __restrict__ out,
+    long long rows, long long nnz, int n_trees, int vs) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    long long lo = indptr[r], hi = indptr[r + 1];
+    if (lo < 0) lo = 0;
+    if (hi > nnz) hi = nnz;
+    float acc[MAXVS];
+#pragma unroll
+    for (int c = 0; c < MAXVS; ++c) acc[c] = 0.f;
+    for (int t = 0; t < n_trees; ++t) {
+        int node = roots[t];
+        int jf = feat[node];
+        while (jf >= 0) {
+            const float x = csr_lookup(indices, data, lo, hi, jf);
+            node = (x <= thr[node]) ? left[node] : right[node];
+            jf = feat[node];
+        }
+        const float* v = values + (long long)left[node] * vs;
+#pragma unroll
+        for (int c = 0; c < MAXVS; ++c)
+            if (c < vs) acc[c] += v[c];
+    }
+    const float inv = 1.f / (float)n_trees;
+#pragma unroll
+    for (int c = 0; c < MAXVS; ++c)
+        if (c < vs) out[r * vs + c] = acc[c] * inv;
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_forest_apply_csr(
+    const long long* __restrict__ indptr, const int* __restrict__ indices,
+    const float* __restrict__ data, const int* __restrict__ feat,
+    const float* __restrict__ thr, const int* __restrict__ left,
+    const int* __restrict__ right, const int* __restrict__ roots,
+    int* __restrict__ out_leaf, long long rows, long long nnz,
+    int n_trees) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    long long lo = indptr[r], hi = indptr[r + 1];
+    if (lo < 0) lo = 0;
+    if (hi > nnz) hi = nnz;
+    for (int t = 0; t < n_trees; ++t) {
+        int node = roots[t];
+        int jf = feat[node];
+        while (jf >= 0) {
+            const float x = csr_lookup(indices, data, lo, hi, jf);
+            node = (x <= thr[node]) ? left[node] : right[node];
+            jf = feat[node];
+        }
+        out_leaf[r * n_trees + t] = node;
+    }
+}
+
+extern "C" hipError_t skdist_forest_predict_csr(
+    const void* indptr, const void* indices, const void* data,
+    const void* feat, const void* thr, const void* left, const void* right,
+    const void* roots, const void* values, void* out, long long rows,
+    long long nnz, int n_trees, int vs, hipStream_t stream) {
+    if (vs > MAXVS) return hipErrorInvalidValue;
+    if (rows <= 0) return hipSuccess;
+    const int blocks = (int)((rows + 255) / 256);
+    hipLaunchKernelGGL(k_forest_predict_csr, dim3(blocks), dim3(256), 0,
+                       stream, (const long long*)indptr,
+                       (const int*)indices, (const float*)data,
+                       (const int*)feat, (const float*)thr,
+                       (const int*)left, (const int*)right,
+                       (const int*)roots, (const float*)values,
+                       (float*)out, rows, nnz, n_trees, vs);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t skdist_forest_apply_csr(
+    const void* indptr, const void* indices, const void* data,
+    const void* feat, const void* thr, const void* left, const void* right,
+    const void* roots, void* out_leaf, long long rows, long long nnz,
+    int n_trees, hipStream_t stream) {
+    if (rows <= 0) return hipSuccess;
+    const int blocks = (int)((rows + 255) / 256);
+    hipLaunchKernelGGL(k_forest_apply_csr, dim3(blocks), dim3(256), 0,
+                       stream, (const long long*)indptr,
+                       (const int*)indices, (const float*)data,
+                       (const int*)feat, (const float*)thr,
+                       (const int*)left, (const int*)right,
+                       (const int*)roots, (int*)out_leaf, rows, nnz,
+                       n_trees);
+    return hipGetLastError();
+}

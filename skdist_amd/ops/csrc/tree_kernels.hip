@@ -497,3 +497,67 @@ extern "C" hipError_t skdist_part_scatter(
                        fp, (int*)sample_idx_out);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------- //
+// K0: CSR -> uint8 codes (BinnedDataset on a scipy-sparse X)
+// grid: grid-stride over rows, one row per workgroup pass; block 256
+//
+//   zc4    [fp/4]       the row pattern of a cell with no stored entry
+//                       (zero_code[j] = #edges[j] < 0.0, pad columns 0),
+//                       packed 4 codes per 32-bit word
+//   edges  [f][nbins-1] f32 ascending per feature
+//   indptr [n+1] int64, indices [nnz] int32, data [nnz] f32 (no duplicate
+//   (row, col) pairs: the host sums them before upload)
+//
+// Pass 1 fills the row with the zero pattern in 4-byte stores (fp % 4 == 0
+// keeps every row base aligned); after the barrier pass 2 overwrites each
+// stored cell with its own code = #edges[col] strictly less than the value
+// (lower bound), so a stored 0.0 lands on zero_code again.
+// ---------------------------------------------------------------------- //
+extern "C" __global__ __launch_bounds__(256) void k_bin_csr(
+    const long long* __restrict__ indptr, const int* __restrict__ indices,
+    const float* __restrict__ data, const float* __restrict__ edges,
+    const unsigned* __restrict__ zc4, unsigned char* __restrict__ codes,
+    long long n, long long nnz, int f, int fp, int nedges) {
+    const int fp4 = fp >> 2;
+    for (long long r = blockIdx.x; r < n; r += gridDim.x) {
+        unsigned char* crow = codes + r * (long long)fp;
+        unsigned* crow4 = (unsigned*)crow;
+        for (int q = threadIdx.x; q < fp4; q += blockDim.x)
+            crow4[q] = zc4[q];
+        __syncthreads();
+        long long lo = indptr[r], hi = indptr[r + 1];
+        if (lo < 0) lo = 0;
+        if (hi > nnz) hi = nnz;
+        for (long long k = lo + threadIdx.x; k < hi; k += blockDim.x) {
+            const int col = indices[k];
+            if ((unsigned)col >= (unsigned)f) continue;
+            const float v = data[k];
+            const float* e = edges + (long long)col * nedges;
+            int a = 0, b = nedges;       // first index with e[idx] >= v
+            while (a < b) {
+                const int mid = (a + b) >> 1;
+                if (e[mid] < v) a = mid + 1; else b = mid;
+            }
+            crow[col] = (unsigned char)a;
+        }
+        // the next row of this workgroup is a different address range,
+        // so no second barrier is needed
+    }
+}
+
+extern "C" hipError_t skdist_bin_csr(
+    const void* indptr, const void* indices, const void* data,
+    const void* edges, const void* zc4, void* codes, long long n,
+    long long nnz, int f, int fp, int nedges, hipStream_t stream) {
+    if (n <= 0) return hipSuccess;
+    if (fp % 4 != 0 || f > fp || nedges < 0 || nedges > 255)
+        return hipErrorInvalidValue;
+    const int blocks = (int)(n < 16384 ? n : 16384);
+    hipLaunchKernelGGL(k_bin_csr, dim3(blocks), dim3(256), 0, stream,
+                       (const long long*)indptr, (const int*)indices,
+                       (const float*)data, (const float*)edges,
+                       (const unsigned*)zc4, (unsigned char*)codes, n, nnz,
+                       f, fp, nedges);
+    return hipGetLastError();
+}

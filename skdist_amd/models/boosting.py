@@ -22,6 +22,21 @@ binned dataset + level-synchronous tree builder as the forests
   * ``n_iter_no_change`` holds out ``validation_fraction`` rows (weight 0
     through the same plane) and stops when their loss stalls for that
     many rounds (sklearn's early-stopping semantics).
+  * ``fit(X, y, sample_weight=...)`` (and the classifier's
+    ``class_weight=None | "balanced" | dict``, expanded per row and
+    multiplied in) rides a real-valued f32 row-weight plane next to the
+    codes (``BinnedDataset.row_w``; k_tree_hist_w / k_tree_split_w on
+    GPU): every histogram cell holds (Σw, Σw·g, Σw·g², row count), so
+    weight sums drive impurity, gain and leaf values while
+    ``min_samples_split`` / ``min_samples_leaf`` stay ROW counts
+    (sklearn's GradientBoosting semantics).  The initial score is the
+    weighted mean / weighted class priors, the Newton leaf refit is
+    Σw·g / Σw·h, the validation loss is the weighted mean over the
+    held-out rows, and rows of weight 0 are folded into the 0/1 mask so
+    they enter no node segment and no count.  A fit without weights
+    takes exactly the unweighted code path and kernels.  Not supported:
+    ``min_weight_fraction_leaf``; the forests keep their own quantised
+    uint8 weight plane.
 
 The CPU path runs the builder's eager torch mirror — correct and
 usable (50 trees on 100k x 20 in ~8 s) but, like the rest of the CPU
@@ -93,6 +108,13 @@ def _seg_sum(vrow, vals, nl):
     return cs.index_select(0, ends[1:]) - cs.index_select(0, ends[:-1])
 
 
+def _wmean(v, w):
+    """Mean of ``v``, weighted by ``w`` when given (device fp64)."""
+    if w is None:
+        return float(v.mean())
+    return float((v * w).sum() / w.sum())
+
+
 class _BaseHistGB(BaseEstimator):
     """NAMING NOTE: despite the ``HistGradientBoosting*`` class names
     (they ARE histogram-binned boosters), the parameter surface is
@@ -125,11 +147,24 @@ class _BaseHistGB(BaseEstimator):
         self.sc = sc
 
     # ------------------------------------------------------------------ #
+    def _row_weights(self, y, sample_weight, n):
+        """Validated fp64 [n] row weights, or None for an unweighted fit
+        (the classifier multiplies its class_weight expansion in)."""
+        if sample_weight is None:
+            return None
+        sw = np.asarray(sample_weight, dtype=np.float64)
+        if sw.shape != (n,):
+            raise ValueError(
+                f"sample_weight must have shape ({n},), got {sw.shape}")
+        if not np.isfinite(sw).all():
+            raise ValueError("sample_weight must be finite")
+        if (sw < 0).any():
+            raise ValueError("sample_weight must be non-negative")
+        if not sw.sum() > 0:
+            raise ValueError("sample_weight must have a positive sum")
+        return sw
+
     def fit(self, X, y, sample_weight=None):
-        if sample_weight is not None:
-            raise NotImplementedError(
-                "sample_weight is not supported by the hist-GBT yet"
-            )
         import scipy.sparse as sp
 
         sparse = sp.issparse(X)
@@ -154,10 +189,18 @@ class _BaseHistGB(BaseEstimator):
             else int(self.n_estimators)
         )
 
-        F, K = self._init_raw(y, n)   # raw scores [n, K]; K columns
+        sw = self._row_weights(y, sample_weight, n)
+        if sw is not None:
+            # the builder's plane is f32; use the same rounded values in
+            # the Newton refit, the priors and the validation loss
+            sw = sw.astype(np.float32).astype(np.float64)
+            if not sw.sum() > 0:
+                raise ValueError("sample_weight must have a positive sum")
+        F, K = self._init_raw(y, n, sw)   # raw scores [n, K]; K columns
         ds = BinnedDataset(
             X, np.zeros(n, dtype=np.float32), device, is_cls=False,
             seed=int(rng.randint(1 << 31)),
+            row_weight=sw,
         )
         builder = ForestBuilder(
             ds, "squared_error", max_depth=self.max_depth,
@@ -179,6 +222,15 @@ class _BaseHistGB(BaseEstimator):
             val_idx = rng.permutation(n)[:vn]
             train_mask = np.ones(n, dtype=np.float32)
             train_mask[val_idx] = 0.0
+            if sw is not None and not sw[val_idx].sum() > 0:
+                raise ValueError(
+                    "the validation slice held out for n_iter_no_change "
+                    "has zero total sample_weight; early stopping cannot "
+                    "score it")
+        if sw is not None and (sw == 0).any():
+            # zero-weight rows enter no node segment and no count
+            nz = (sw > 0).astype(np.float32)
+            train_mask = nz if train_mask is None else train_mask * nz
         best_loss = np.inf
         stall = 0
 
@@ -202,6 +254,14 @@ class _BaseHistGB(BaseEstimator):
             torch.as_tensor(val_idx, dtype=torch.int64, device=dev)
             if val_idx is not None else None
         )
+        sw_t = (
+            torch.as_tensor(sw, dtype=torch.float64, device=dev)
+            if sw is not None else None
+        )
+        val_w = (
+            sw_t.index_select(0, val_t)
+            if sw_t is not None and val_t is not None else None
+        )
 
         stages = []
         for _ in range(n_rounds):
@@ -219,6 +279,9 @@ class _BaseHistGB(BaseEstimator):
                 torch.as_tensor(mask, device=dev) if mask is not None
                 else None
             )
+            if sw_t is not None:
+                # Newton sums weigh each row by mask * sample_weight
+                mask_t = sw_t if mask_t is None else mask_t * sw_t
             grad, hess = self._gradients_t(Ft)   # [n, K] device fp64
             round_trees = []
             for k in range(K):
@@ -235,7 +298,7 @@ class _BaseHistGB(BaseEstimator):
                 round_trees.append(tree)
             stages.append(round_trees)
             if val_t is not None:
-                loss = self._loss_t(val_t, Ft)
+                loss = self._loss_t(val_t, Ft, val_w)
                 if loss < best_loss - self.tol:
                     best_loss = loss
                     stall = 0
@@ -259,8 +322,8 @@ class _BaseHistGB(BaseEstimator):
         (subsampled) rows: value = scale * Σg / Σh per leaf — computed
         on device with a deterministic sort + cumsum segment sum."""
         scale = self._newton_scale(K)
-        if scale is None:  # squared loss: mean residual is already right
-            return
+        if scale is None:  # squared loss: (weighted) mean residual is
+            return         # already the Newton step
         if mask_t is not None:
             g = g * mask_t
             h = h * mask_t
@@ -385,18 +448,20 @@ def _strip(est):
 class HistGradientBoostingRegressor(RegressorMixin, _BaseHistGB):
     """Least-squares gradient boosting on binned HistTrees."""
 
-    def _init_raw(self, y, n):
+    def _init_raw(self, y, n, sw=None):
         self._yv = np.asarray(y, dtype=np.float64)
-        self.init_raw_ = float(self._yv.mean())
+        self.init_raw_ = float(
+            self._yv.mean() if sw is None
+            else np.average(self._yv, weights=sw))
         return np.full((n, 1), self.init_raw_), 1
 
     def _to_device_targets(self, dev):
         self._yv_t = torch.as_tensor(self._yv, dtype=torch.float64,
                                      device=dev)
 
-    def _loss_t(self, idx, Ft):
+    def _loss_t(self, idx, Ft, w=None):
         d = self._yv_t.index_select(0, idx) - Ft.index_select(0, idx)[:, 0]
-        return float((d * d).mean())
+        return _wmean(d * d, w)
 
     def _base_raw(self):
         return np.array([self.init_raw_])
@@ -422,7 +487,34 @@ class HistGradientBoostingClassifier(ClassifierMixin, _BaseHistGB):
 
     _is_classifier = True
 
-    def _init_raw(self, y, n):
+    def __init__(self, n_estimators=100, learning_rate=0.1, max_depth=3,
+                 subsample=1.0, min_samples_split=2, min_samples_leaf=1,
+                 max_features=None, n_iter_no_change=None,
+                 validation_fraction=0.1, tol=1e-4, random_state=None,
+                 max_iter=None, sc=None, class_weight=None):
+        super().__init__(
+            n_estimators=n_estimators, learning_rate=learning_rate,
+            max_depth=max_depth, subsample=subsample,
+            min_samples_split=min_samples_split,
+            min_samples_leaf=min_samples_leaf, max_features=max_features,
+            n_iter_no_change=n_iter_no_change,
+            validation_fraction=validation_fraction, tol=tol,
+            random_state=random_state, max_iter=max_iter, sc=sc)
+        self.class_weight = class_weight
+
+    def _row_weights(self, y, sample_weight, n):
+        sw = super()._row_weights(y, sample_weight, n)
+        cw = getattr(self, "class_weight", None)
+        if cw is None:
+            return sw
+        from sklearn.utils.class_weight import compute_sample_weight
+
+        cwv = np.asarray(compute_sample_weight(cw, np.asarray(y)),
+                         dtype=np.float64)
+        return super()._row_weights(
+            y, cwv if sw is None else sw * cwv, n)
+
+    def _init_raw(self, y, n, sw=None):
         self.classes_, enc = np.unique(np.asarray(y), return_inverse=True)
         self._enc = enc
         k = len(self.classes_)
@@ -430,9 +522,16 @@ class HistGradientBoostingClassifier(ClassifierMixin, _BaseHistGB):
             raise ValueError("need at least 2 classes")
         eps = 1e-12
         if k == 2:
-            p = np.clip(enc.mean(), eps, 1 - eps)
+            p = np.clip(
+                enc.mean() if sw is None else np.average(enc, weights=sw),
+                eps, 1 - eps)
             self.init_raw_ = np.array([np.log(p / (1 - p))])
             return np.tile(self.init_raw_, (n, 1)), 1
+        if sw is not None:
+            cnt = np.bincount(enc, weights=sw, minlength=k)
+            pri = np.clip(cnt / cnt.sum(), eps, None)
+            self.init_raw_ = np.log(pri)
+            return np.tile(self.init_raw_, (n, 1)), k
         pri = np.clip(np.bincount(enc, minlength=k) / n, eps, None)
         self.init_raw_ = np.log(pri)
         return np.tile(self.init_raw_, (n, 1)), k
@@ -459,17 +558,18 @@ class HistGradientBoostingClassifier(ClassifierMixin, _BaseHistGB):
     def _newton_scale(self, K):
         return 1.0 if K == 1 else (K - 1.0) / K
 
-    def _loss_t(self, idx, Ft):
-        # mean deviance (neg log-likelihood) on the validation slice
+    def _loss_t(self, idx, Ft, w=None):
+        # (weighted) mean deviance (neg log-likelihood) on the validation
+        # slice
         z = Ft.index_select(0, idx)
         t = self._enc_t.index_select(0, idx)
         if Ft.shape[1] == 1:
             z0 = z[:, 0]
-            return float(
-                (torch.nn.functional.softplus(z0)
-                 - t.to(torch.float64) * z0).mean())
+            return _wmean(
+                torch.nn.functional.softplus(z0)
+                - t.to(torch.float64) * z0, w)
         lse = torch.logsumexp(z, dim=1)
-        return float((lse - z.gather(1, t.unsqueeze(1))[:, 0]).mean())
+        return _wmean(lse - z.gather(1, t.unsqueeze(1))[:, 0], w)
 
     def decision_function(self, X):
         r = self._raw_scores(X)

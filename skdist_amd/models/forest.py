@@ -288,10 +288,16 @@ class BinnedDataset:
     A scipy-sparse X is binned from its CSR arrays (k_bin_csr on GPU, a
     torch mirror on CPU) into the same ``edges`` and ``codes`` the dense
     constructor computes for ``X.toarray()``; only the uint8 code matrix
-    is dense."""
+    is dense.
+
+    ``row_weight`` (regression mode only) puts a real-valued f32 [n]
+    weight plane ``row_w`` next to the codes.  The builder then keeps four
+    statistics per histogram cell, (W, Wy, Wyy, C): weight sums drive
+    impurity, gain and leaf values while the row count C keeps
+    ``min_samples_*`` counts.  Without it nothing changes."""
 
     def __init__(self, X, y, device, is_cls, classes=None, nbins=256,
-                 max_bin_sample=200_000, seed=0):
+                 max_bin_sample=200_000, seed=0, row_weight=None):
         import scipy.sparse as sp
 
         self.device = torch.device(device)
@@ -300,6 +306,26 @@ class BinnedDataset:
         else:
             self._init_codes_dense(X, nbins, max_bin_sample, seed)
         self._init_targets(y, is_cls, classes)
+        self.row_w = None
+        if row_weight is not None:
+            self.set_row_weight(row_weight)
+
+    def set_row_weight(self, row_weight):
+        """Attach the f32 row-weight plane (before a ForestBuilder is
+        constructed on this dataset: the builder sizes its LDS feature
+        groups from ``S``)."""
+        if self.is_cls:
+            raise ValueError(
+                "row_weight is supported for regression targets only "
+                "(classification forests use the uint8 weight plane)")
+        rw = np.ascontiguousarray(row_weight, dtype=np.float32)
+        if rw.shape != (self.n,):
+            raise ValueError(
+                f"row_weight must have shape ({self.n},), got {rw.shape}")
+        if not np.isfinite(rw).all() or (rw < 0).any():
+            raise ValueError("row_weight must be finite and non-negative")
+        self.row_w = torch.as_tensor(rw, device=self.device)
+        self.S = 4  # (W, Wy, Wyy, C)
 
     def _init_codes_csr(self, X, nbins, max_bin_sample, seed):
         import os
@@ -564,6 +590,8 @@ class ForestBuilder:
                 "SKDIST_AMD_ALLOW_EAGER=1 (the HIP kernels are the "
                 "production path)")
         self.engine = engine
+        # index of the row-count stat (datasets with a row-weight plane)
+        self.cnt_stat = 3 if getattr(ds, "row_w", None) is not None else -1
         # features per LDS group for the hist kernel
         per_feat = ds.nbins * ds.S * 4
         fg = max(1, min(ds.f, self.LDS_BUDGET_BYTES // per_feat))
@@ -661,12 +689,18 @@ class ForestBuilder:
             (bfeat, bbin, bgain, bimp, bwl, pstats, lstats) = dec
 
             wp = pstats.sum(axis=1) if ds.is_cls else pstats[:, 0]
+            counted = self.cnt_stat >= 0
+            # min_samples_split compares row counts when the weights are
+            # real numbers; the weight sums drive everything else
+            cp = pstats[:, self.cnt_stat] if counted else wp
             if depth == 0:
-                root_w[fr_tree] = np.maximum(wp, 1.0)
+                root_w[fr_tree] = (
+                    np.where(wp > 0, wp, 1.0) if counted
+                    else np.maximum(wp, 1.0))
             ok = (
                 (bfeat >= 0)
                 & (depth < self.max_depth)
-                & (wp >= self._mss_eff)
+                & (cp >= self._mss_eff)
                 & (bgain > 0)
                 & ((wp / root_w[fr_tree]) * bgain >= self.mid - 1e-12)
             )
@@ -718,15 +752,17 @@ class ForestBuilder:
             else:
                 wl = ls[:, 0]
                 wr = rs[:, 0]
+            cl = ls[:, self.cnt_stat] if counted else wl
+            cr = rs[:, self.cnt_stat] if counted else wr
             nrows_l = nl.astype(np.int64)
             nrows_r = fr_count[part_idx] - nrows_l
             st_l = fr_start[part_idx]
             st_r = st_l + nrows_l
 
             can_grow = depth + 1 < self.max_depth
-            grow_l = (can_grow & (wl >= self._mss_eff) & (nrows_l > 1)
+            grow_l = (can_grow & (cl >= self._mss_eff) & (nrows_l > 1)
                       & (self._impurity_vec(ls, wl) > 1e-12))
-            grow_r = (can_grow & (wr >= self._mss_eff) & (nrows_r > 1)
+            grow_r = (can_grow & (cr >= self._mss_eff) & (nrows_r > 1)
                       & (self._impurity_vec(rs, wr) > 1e-12))
             st.make_leaves(gl[~grow_l], self._leaf_values_vec(ls[~grow_l]))
             st.make_leaves(gr[~grow_r], self._leaf_values_vec(rs[~grow_r]))
@@ -930,6 +966,11 @@ class ForestBuilder:
             return
         chunks_np = self._chunk_table(tree, start, count, slot)
         chunks = torch.as_tensor(chunks_np, device=dev)
+        if self.cnt_stat >= 0:
+            self._ext.tree_hist_w(
+                ds.codes, ds.y_f, ds.row_w, weights, si, chunks, hist,
+                ds.n, ds.f, ds.nbins, self.fg)
+            return
         self._ext.tree_hist(
             ds.codes, ds.y_int if ds.is_cls else torch.empty(
                 0, dtype=torch.int32, device=dev),
@@ -954,12 +995,20 @@ class ForestBuilder:
         out_imp = fbuf[2 * NF: 3 * NF]
         out_stats = fbuf[3 * NF: (3 + S) * NF].view(NF, S)
         out_lstats = fbuf[(3 + S) * NF:].view(NF, S)
-        self._ext.tree_split(
-            hist, seed_t, ds.f, ds.nbins, S, int(ds.is_cls), self.crit,
-            self.m_features, int(self.extra_mode),
-            float(getattr(self, "_msl_eff", self.msl)),
-            out_feat, out_bin, out_wl, out_gain, out_imp, out_stats,
-            out_lstats)
+        if self.cnt_stat >= 0:
+            self._ext.tree_split_w(
+                hist, seed_t, ds.f, ds.nbins, S, int(ds.is_cls), self.crit,
+                self.m_features, int(self.extra_mode),
+                float(getattr(self, "_msl_eff", self.msl)),
+                out_feat, out_bin, out_wl, out_gain, out_imp, out_stats,
+                out_lstats, self.cnt_stat)
+        else:
+            self._ext.tree_split(
+                hist, seed_t, ds.f, ds.nbins, S, int(ds.is_cls), self.crit,
+                self.m_features, int(self.extra_mode),
+                float(getattr(self, "_msl_eff", self.msl)),
+                out_feat, out_bin, out_wl, out_gain, out_imp, out_stats,
+                out_lstats)
         ih = ibuf.cpu().numpy()
         fh = fbuf.cpu().numpy().astype(np.float64)
         return (ih[:NF].astype(np.int64),
@@ -1023,6 +1072,12 @@ class ForestBuilder:
                 base = (torch.arange(f, device=ds.device)[:, None]
                         * nbins + codes) * S
                 hv = hist.view(-1)
+                if self.cnt_stat >= 0:
+                    # (W, Wy, Wyy, C): C counts the uint8 multiplicity m,
+                    # the weight is m * row_w (k_tree_hist_w)
+                    hv.scatter_add_(0, (base + self.cnt_stat).reshape(-1),
+                                    w.unsqueeze(0).expand(f, -1).reshape(-1))
+                    w = w * ds.row_w[rows]
                 hv.scatter_add_(0, base.reshape(-1),
                                 w.unsqueeze(0).expand(f, -1).reshape(-1))
                 hv.scatter_add_(0, (base + 1).reshape(-1),
@@ -1084,7 +1139,14 @@ class ForestBuilder:
         with np.errstate(invalid="ignore"):
             gain = imp_p - (wl * imp_l + wr * imp_r) / max(wp, 1e-30)
         msl = getattr(self, "_msl_eff", self.msl)
-        valid = (wl >= msl) & (wr >= msl) & sel[:, None]
+        if self.cnt_stat >= 0:
+            # k_tree_split_w: min-leaf on row counts, weight on both sides
+            cl = cum[:, :, self.cnt_stat]
+            cr = parent[self.cnt_stat] - cl
+            valid = ((cl >= msl) & (cr >= msl) & (wl > 0) & (wr > 0)
+                     & sel[:, None])
+        else:
+            valid = (wl >= msl) & (wr >= msl) & sel[:, None]
         if self.extra_mode:
             extra_ok = np.zeros_like(valid)
             wbin = h.sum(axis=2) if ds.is_cls else h[:, :, 0]

@@ -399,6 +399,17 @@ extern "C" hipError_t skdist_tree_split(
     float min_leaf_w, void* out_feat, void* out_bin, void* out_wl,
     void* out_gain, void* out_imp, void* out_stats, void* out_lstats,
     hipStream_t stream);
+extern "C" hipError_t skdist_tree_hist_w(
+    const void* codes, const void* y_f, const void* row_w,
+    const void* weights, const void* sample_idx, const void* chunks,
+    void* hist, long long n, int f, int fp, int nbins, int fg,
+    int n_chunks, hipStream_t stream);
+extern "C" hipError_t skdist_tree_split_w(
+    const void* hist, const void* node_seed, int n_frontier, int f,
+    int nbins, int S, int is_cls, int crit, int m_features, int extra_mode,
+    float min_leaf, int cnt_stat, void* out_feat, void* out_bin,
+    void* out_wl, void* out_gain, void* out_imp, void* out_stats,
+    void* out_lstats, hipStream_t stream);
 extern "C" hipError_t skdist_part_count(
     const void* codes, const void* sample_idx, const void* chunks,
     const void* split_feat, const void* split_bin, long long n, int fp,
@@ -490,6 +501,97 @@ void tree_split(torch::Tensor hist, torch::Tensor node_seed, int64_t f,
         out_gain.data_ptr(), out_imp.data_ptr(), out_stats.data_ptr(),
         out_lstats.data_ptr(), stream);
     TORCH_CHECK(err == hipSuccess, "tree_split: ", hipGetErrorString(err));
+}
+
+void tree_hist_w(torch::Tensor codes, torch::Tensor y_f, torch::Tensor row_w,
+                 torch::Tensor weights, torch::Tensor sample_idx,
+                 torch::Tensor chunks, torch::Tensor hist, int64_t n,
+                 int64_t f, int64_t nbins, int64_t fg) {
+    for (auto* t :
+         {&codes, &y_f, &row_w, &weights, &sample_idx, &chunks, &hist}) {
+        CHECK_DEV(*t);
+        CHECK_CONT(*t);
+    }
+    TORCH_CHECK(codes.scalar_type() == torch::kUInt8, "codes must be u8");
+    TORCH_CHECK(weights.scalar_type() == torch::kUInt8,
+                "weights must be u8");
+    TORCH_CHECK(y_f.scalar_type() == torch::kFloat32, "y_f must be f32");
+    TORCH_CHECK(row_w.scalar_type() == torch::kFloat32,
+                "row_w must be f32");
+    TORCH_CHECK(hist.scalar_type() == torch::kFloat32, "hist must be f32");
+    TORCH_CHECK(sample_idx.scalar_type() == torch::kInt32,
+                "sample_idx must be i32");
+    TORCH_CHECK(chunks.scalar_type() == torch::kInt32,
+                "chunks must be i32");
+    TORCH_CHECK(codes.dim() == 2 && codes.size(0) == n &&
+                    codes.size(1) % 4 == 0 && f >= 1 && f <= codes.size(1),
+                "codes must be [n, fp] with fp % 4 == 0 and f <= fp");
+    TORCH_CHECK(row_w.numel() == n, "row_w must have n elements");
+    TORCH_CHECK(y_f.numel() == n, "y_f must have n elements");
+    TORCH_CHECK(weights.dim() == 2 && weights.size(1) == n &&
+                    sample_idx.dim() == 2 && sample_idx.size(1) == n &&
+                    sample_idx.size(0) == weights.size(0),
+                "weights and sample_idx must be [TB, n]");
+    TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 4,
+                "chunks must be [n_chunks, 4]");
+    TORCH_CHECK(nbins >= 1 && nbins <= 256, "nbins must be in [1, 256]");
+    TORCH_CHECK(hist.dim() == 4 && hist.size(1) == f &&
+                    hist.size(2) == nbins && hist.size(3) == 4,
+                "hist must be [NF, f, nbins, 4]");
+    TORCH_CHECK(fg >= 1 && fg * nbins * 16 <= 64 * 1024,
+                "fg * nbins * 16 bytes must fit 64 KiB of LDS");
+    const int64_t fp = codes.size(1);
+    auto stream = c10::hip::getCurrentHIPStream().stream();
+    hipError_t err = skdist_tree_hist_w(
+        codes.data_ptr(), y_f.data_ptr(), row_w.data_ptr(),
+        weights.data_ptr(), sample_idx.data_ptr(), chunks.data_ptr(),
+        hist.data_ptr(), n, (int)f, (int)fp, (int)nbins, (int)fg,
+        (int)chunks.size(0), stream);
+    TORCH_CHECK(err == hipSuccess, "tree_hist_w: ", hipGetErrorString(err));
+}
+
+void tree_split_w(torch::Tensor hist, torch::Tensor node_seed, int64_t f,
+                  int64_t nbins, int64_t S, int64_t is_cls, int64_t crit,
+                  int64_t m_features, int64_t extra_mode, double min_leaf,
+                  torch::Tensor out_feat, torch::Tensor out_bin,
+                  torch::Tensor out_wl, torch::Tensor out_gain,
+                  torch::Tensor out_imp, torch::Tensor out_stats,
+                  torch::Tensor out_lstats, int64_t cnt_stat) {
+    const int64_t NF = node_seed.size(0);
+    for (auto* t : {&hist, &node_seed, &out_feat, &out_bin, &out_wl,
+                    &out_gain, &out_imp, &out_stats, &out_lstats}) {
+        CHECK_DEV(*t);
+        CHECK_CONT(*t);
+    }
+    TORCH_CHECK(hist.scalar_type() == torch::kFloat32, "hist must be f32");
+    TORCH_CHECK(node_seed.scalar_type() == torch::kInt32,
+                "node_seed must be i32");
+    TORCH_CHECK(out_feat.scalar_type() == torch::kInt32 &&
+                    out_bin.scalar_type() == torch::kInt32,
+                "out_feat/out_bin must be i32");
+    for (auto* t : {&out_wl, &out_gain, &out_imp, &out_stats, &out_lstats})
+        TORCH_CHECK(t->scalar_type() == torch::kFloat32,
+                    "float outputs must be f32");
+    TORCH_CHECK(S >= 1 && S <= 32, "tree_split_w supports <= 32 stats");
+    TORCH_CHECK(cnt_stat >= -1 && cnt_stat < S,
+                "cnt_stat must be -1 or a stat index");
+    TORCH_CHECK(hist.numel() >= NF * f * nbins * S, "hist too small");
+    TORCH_CHECK(out_feat.numel() >= NF && out_bin.numel() >= NF &&
+                    out_wl.numel() >= NF && out_gain.numel() >= NF &&
+                    out_imp.numel() >= NF && out_stats.numel() >= NF * S &&
+                    out_lstats.numel() >= NF * S,
+                "outputs too small for the frontier");
+    if (NF == 0) return;
+    auto stream = c10::hip::getCurrentHIPStream().stream();
+    hipError_t err = skdist_tree_split_w(
+        hist.data_ptr(), node_seed.data_ptr(), (int)NF, (int)f, (int)nbins,
+        (int)S, (int)is_cls, (int)crit, (int)m_features, (int)extra_mode,
+        (float)min_leaf, (int)cnt_stat, out_feat.data_ptr(),
+        out_bin.data_ptr(), out_wl.data_ptr(), out_gain.data_ptr(),
+        out_imp.data_ptr(), out_stats.data_ptr(), out_lstats.data_ptr(),
+        stream);
+    TORCH_CHECK(err == hipSuccess, "tree_split_w: ",
+                hipGetErrorString(err));
 }
 
 void part_count(torch::Tensor codes, torch::Tensor sample_idx,
@@ -787,6 +889,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "UTF-8 tokenize + murmur3 feature hashing -> COO pairs");
     m.def("tree_hist", &tree_hist, "per-(node,feature,bin) stats");
     m.def("tree_split", &tree_split, "best split per frontier node");
+    m.def("tree_hist_w", &tree_hist_w,
+          "per-(node,feature,bin) (W,Wy,Wyy,C) stats with f32 row weights");
+    m.def("tree_split_w", &tree_split_w,
+          "best split per frontier node, min-leaf on a count stat");
     m.def("part_count", &part_count, "partition phase A: left counts");
     m.def("part_scatter", &part_scatter, "partition phase B: scatter");
     m.def("forest_predict", &forest_predict, "batched forest inference");

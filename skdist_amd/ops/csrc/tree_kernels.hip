@@ -6,9 +6,12 @@
 // level-synchronously against ONE HBM-resident binned copy of X:
 //
 //   K1 k_tree_hist:    per-(node,feature,bin) weighted stats, LDS-staged
+//      k_tree_hist_w:  the regression stats with a real-valued f32 row-weight
+//                      plane on top of the uint8 one, plus a row-count slot
 //   K2 k_tree_split:   best (feature,bin) per frontier node — gini /
 //                      entropy / mse scan with exact max_features
 //                      subsampling and ExtraTrees random-threshold mode
+//      k_tree_split_w: same scan; the min-leaf test reads a count slot
 //   K3 k_part_count:   per-chunk left-row counts for the stable partition
 //   K4 k_part_scatter: stable partition of each node's sample segment
 //
@@ -19,14 +22,21 @@
 //                                     padded to a multiple of 4 for uchar4 loads)
 //   sample_idx [TB][n]   int32   per-tree row ids, node segments contiguous
 //   weights    [TB][n]   uint8   bootstrap multiplicities (0 = out of bag)
+//   row_w      [n]       f32     real-valued row weights, shared by all trees
+//                                     of the batch (k_tree_hist_w only)
 //   hist       [NF][f][nbins][S] f32   S = n_classes (cls) | 3 (w,wy,wyy)
+//                                       | 4 (W,Wy,Wyy,C) with row_w, where
+//                                       w = weights*row_w and C = Σ weights
 //   chunks     [n_chunks][4] int32     {node_slot, tree_slot, row_start,
 //                                       row_count}
 //
 // Determinism: classification stats are integer-valued f32 atomics (exact,
 // order-independent); regression wy/wyy sums are fp32 atomics whose
 // rounding depends on arrival order — ties between split candidates are
-// broken by (feature, bin) so only near-exact-tie splits can differ.
+// broken by (feature, bin) so only near-exact-tie splits can differ.  With
+// row_w the W slot is a real-valued sum too and rounds the same way; the
+// count slot C is integer-valued like the class counts, so it is exact and
+// the min_samples_* tests that read it do not depend on arrival order.
 #include "common.h"
 
 #define WAVE 64
@@ -128,6 +138,80 @@ extern "C" __global__ __launch_bounds__(256) void k_tree_hist(
 }
 
 // ---------------------------------------------------------------------- //
+// K1w: histogram build with a real-valued row-weight plane (regression /
+// gradient stats only).  Same grid, chunk table and LDS staging as
+// k_tree_hist; four stats per cell: W = Σ m·row_w, Wy, Wyy and the row
+// count C = Σ m (m = the tree's uint8 multiplicity).
+// dynamic LDS: fg * nbins * 4 floats
+// ---------------------------------------------------------------------- //
+extern "C" __global__ __launch_bounds__(256) void k_tree_hist_w(
+    const unsigned char* __restrict__ codes,    // [n][fp] row-major
+    const float* __restrict__ y_f,              // [n]
+    const float* __restrict__ row_w,            // [n]
+    const unsigned char* __restrict__ weights,  // [TB][n]
+    const int* __restrict__ sample_idx,         // [TB][n]
+    const int* __restrict__ chunks,             // [n_chunks][4]
+    float* __restrict__ hist,                   // [NF][f][nbins][4]
+    long long n, int f, int fp, int nbins, int fg) {
+    extern __shared__ float lds[];
+    const int chunk = blockIdx.x;
+    const int g0 = blockIdx.y * fg;
+    const int nf_g = min(fg, f - g0);
+    const int node_slot = chunks[chunk * 4 + 0];
+    const int tree_slot = chunks[chunk * 4 + 1];
+    const int row_start = chunks[chunk * 4 + 2];
+    const int row_count = chunks[chunk * 4 + 3];
+
+    const int lds_sz = nf_g * nbins * 4;
+    for (int i = threadIdx.x; i < lds_sz; i += blockDim.x) lds[i] = 0.f;
+    __syncthreads();
+
+    const int* si = sample_idx + (long long)tree_slot * n + row_start;
+    const unsigned char* wrow = weights + (long long)tree_slot * n;
+    const bool vec = (g0 & 3) == 0;
+    for (int r = threadIdx.x; r < row_count; r += blockDim.x) {
+        const int i = si[r];
+        const float m = (float)wrow[i];
+        const float w = m * row_w[i];
+        const float yv = y_f[i];
+        const float v1 = w * yv;
+        const float v2 = w * yv * yv;
+        const unsigned char* crow = codes + (long long)i * fp + g0;
+        if (vec) {
+            const uchar4v* c4 = (const uchar4v*)crow;
+            for (int q = 0; q * 4 < nf_g; ++q) {
+                const uchar4v b4 = c4[q];
+                #pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const int jj = q * 4 + t;
+                    if (jj >= nf_g) break;
+                    float* h = lds + ((jj * nbins + (int)b4[t]) * 4);
+                    atomicAdd(h + 0, w);
+                    atomicAdd(h + 1, v1);
+                    atomicAdd(h + 2, v2);
+                    atomicAdd(h + 3, m);
+                }
+            }
+        } else {
+            for (int jj = 0; jj < nf_g; ++jj) {
+                float* h = lds + ((jj * nbins + (int)crow[jj]) * 4);
+                atomicAdd(h + 0, w);
+                atomicAdd(h + 1, v1);
+                atomicAdd(h + 2, v2);
+                atomicAdd(h + 3, m);
+            }
+        }
+    }
+    __syncthreads();
+
+    float* gh = hist + ((long long)node_slot * f + g0) * nbins * 4;
+    for (int i = threadIdx.x; i < lds_sz; i += blockDim.x) {
+        const float v = lds[i];
+        if (v != 0.f) atomicAdd(gh + i, v);
+    }
+}
+
+// ---------------------------------------------------------------------- //
 // K2: split finding — one 256-thread block per frontier node
 // ---------------------------------------------------------------------- //
 #define CRIT_GINI 0
@@ -159,7 +243,12 @@ impurity(const float* s, float w, int S, int is_cls, int crit) {
     return v > 0.f ? v : 0.f;
 }
 
-extern "C" __global__ __launch_bounds__(256) void k_tree_split(
+// COUNTED: min_samples_leaf stays a ROW count when the weights are real
+// numbers — the min-leaf test reads the integer-valued stat cnt_stat
+// instead of the weight sums, and a candidate also needs weight on both
+// sides.  Impurity, gain, tie-break and outputs are the same either way.
+template <bool COUNTED>
+static __device__ __forceinline__ void tree_split_body(
     const float* __restrict__ hist,        // [NF][f][nbins][S]
     const unsigned* __restrict__ node_seed,  // [NF]
     int f, int nbins, int S, int is_cls, int crit, int m_features,
@@ -170,8 +259,8 @@ extern "C" __global__ __launch_bounds__(256) void k_tree_split(
     float* __restrict__ out_gain, // [NF]  impurity improvement (unscaled)
     float* __restrict__ out_imp,  // [NF]  parent impurity
     float* __restrict__ out_stats,  // [NF][S] parent stat totals
-    float* __restrict__ out_lstats  // [NF][S] winning split's left stats
-) {
+    float* __restrict__ out_lstats, // [NF][S] winning split's left stats
+    int cnt_stat) {
     const int node = blockIdx.x;
     const unsigned seed = node_seed[node];
     const float* H = hist + (long long)node * f * nbins * S;
@@ -264,7 +353,14 @@ extern "C" __global__ __launch_bounds__(256) void k_tree_split(
             }
             if (extra_mode && b != rand_bin) continue;
             const float wr = wp - wl;
-            if (wl < min_leaf_w || wr < min_leaf_w) continue;
+            if (COUNTED) {
+                const float cl = left[cnt_stat];
+                const float cr = s_parent[cnt_stat] - cl;
+                if (cl < min_leaf_w || cr < min_leaf_w) continue;
+                if (!(wl > 0.f && wr > 0.f)) continue;
+            } else {
+                if (wl < min_leaf_w || wr < min_leaf_w) continue;
+            }
             const float imp_l = impurity(left, wl, S, is_cls, crit);
             float right[36];
             for (int c = 0; c < S; ++c) right[c] = s_parent[c] - left[c];
@@ -340,6 +436,34 @@ extern "C" __global__ __launch_bounds__(256) void k_tree_split(
         }
         out_lstats[(long long)node * S + c] = acc;
     }
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_tree_split(
+    const float* __restrict__ hist, const unsigned* __restrict__ node_seed,
+    int f, int nbins, int S, int is_cls, int crit, int m_features,
+    int extra_mode, float min_leaf_w, int* __restrict__ out_feat,
+    int* __restrict__ out_bin, float* __restrict__ out_wl,
+    float* __restrict__ out_gain, float* __restrict__ out_imp,
+    float* __restrict__ out_stats, float* __restrict__ out_lstats) {
+    tree_split_body<false>(hist, node_seed, f, nbins, S, is_cls, crit,
+                           m_features, extra_mode, min_leaf_w, out_feat,
+                           out_bin, out_wl, out_gain, out_imp, out_stats,
+                           out_lstats, -1);
+}
+
+// min_leaf_w is a row-count threshold here; cnt_stat in [0, S)
+extern "C" __global__ __launch_bounds__(256) void k_tree_split_w(
+    const float* __restrict__ hist, const unsigned* __restrict__ node_seed,
+    int f, int nbins, int S, int is_cls, int crit, int m_features,
+    int extra_mode, float min_leaf_w, int* __restrict__ out_feat,
+    int* __restrict__ out_bin, float* __restrict__ out_wl,
+    float* __restrict__ out_gain, float* __restrict__ out_imp,
+    float* __restrict__ out_stats, float* __restrict__ out_lstats,
+    int cnt_stat) {
+    tree_split_body<true>(hist, node_seed, f, nbins, S, is_cls, crit,
+                          m_features, extra_mode, min_leaf_w, out_feat,
+                          out_bin, out_wl, out_gain, out_imp, out_stats,
+                          out_lstats, cnt_stat);
 }
 
 // ---------------------------------------------------------------------- //
@@ -454,6 +578,26 @@ extern "C" hipError_t skdist_tree_hist(
     return hipGetLastError();
 }
 
+extern "C" hipError_t skdist_tree_hist_w(
+    const void* codes, const void* y_f, const void* row_w,
+    const void* weights, const void* sample_idx, const void* chunks,
+    void* hist, long long n, int f, int fp, int nbins, int fg,
+    int n_chunks, hipStream_t stream) {
+    if (n_chunks <= 0) return hipSuccess;
+    const size_t lds = (size_t)fg * nbins * 4 * sizeof(float);
+    if (fg <= 0 || f <= 0 || fp % 4 != 0 || f > fp || nbins <= 0 ||
+        nbins > 256 || lds > 64 * 1024)
+        return hipErrorInvalidValue;
+    const int n_groups = (f + fg - 1) / fg;
+    hipLaunchKernelGGL(k_tree_hist_w, dim3(n_chunks, n_groups), dim3(256),
+                       lds, stream, (const unsigned char*)codes,
+                       (const float*)y_f, (const float*)row_w,
+                       (const unsigned char*)weights,
+                       (const int*)sample_idx, (const int*)chunks,
+                       (float*)hist, n, f, fp, nbins, fg);
+    return hipGetLastError();
+}
+
 extern "C" hipError_t skdist_tree_split(
     const void* hist, const void* node_seed, int n_frontier, int f,
     int nbins, int S, int is_cls, int crit, int m_features, int extra_mode,
@@ -470,6 +614,31 @@ extern "C" hipError_t skdist_tree_split(
                        (int*)out_feat, (int*)out_bin, (float*)out_wl,
                        (float*)out_gain, (float*)out_imp,
                        (float*)out_stats, (float*)out_lstats);
+    return hipGetLastError();
+}
+
+// cnt_stat < 0 is today's weight-sum rule (k_tree_split itself)
+extern "C" hipError_t skdist_tree_split_w(
+    const void* hist, const void* node_seed, int n_frontier, int f,
+    int nbins, int S, int is_cls, int crit, int m_features, int extra_mode,
+    float min_leaf, int cnt_stat, void* out_feat, void* out_bin,
+    void* out_wl, void* out_gain, void* out_imp, void* out_stats,
+    void* out_lstats, hipStream_t stream) {
+    if (cnt_stat < 0)
+        return skdist_tree_split(hist, node_seed, n_frontier, f, nbins, S,
+                                 is_cls, crit, m_features, extra_mode,
+                                 min_leaf, out_feat, out_bin, out_wl,
+                                 out_gain, out_imp, out_stats, out_lstats,
+                                 stream);
+    if (cnt_stat >= S || S > 32) return hipErrorInvalidValue;
+    const int threads = f >= 192 ? 256 : (f >= 96 ? 128 : 64);
+    hipLaunchKernelGGL(k_tree_split_w, dim3(n_frontier), dim3(threads), 0,
+                       stream, (const float*)hist,
+                       (const unsigned*)node_seed, f, nbins, S, is_cls,
+                       crit, m_features, extra_mode, min_leaf,
+                       (int*)out_feat, (int*)out_bin, (float*)out_wl,
+                       (float*)out_gain, (float*)out_imp,
+                       (float*)out_stats, (float*)out_lstats, cnt_stat);
     return hipGetLastError();
 }
 

@@ -1,0 +1,336 @@
+"""sample_weight / class_weight for the boosted family (GPU tier):
+k_tree_hist_w / k_tree_split_w and the device fit built on them.
+
+The kernel tests use values whose every partial sum is exactly
+representable in f32 (row_w in {0.25..2.0}, integer y in [-4, 4], uint8
+multiplicities in {0..3}: largest term 3*2*16 = 96 with quantum 1/4, worst
+sum over 33 000 rows 3.2 M < 2^22), so the arrival order of the atomics
+cannot matter and equality with the fp64 host reference is bitwise."""
+
+import numpy as np
+import pytest
+import torch
+
+pytestmark = pytest.mark.gpu
+
+if torch.cuda.is_available():
+    from skdist_amd.models import (
+        HistGradientBoostingClassifier,
+        HistGradientBoostingRegressor,
+    )
+    from skdist_amd.models.forest import BinnedDataset, ForestBuilder
+    from skdist_amd.ops import require_hip
+
+CHUNK_ROWS = 32768
+NBINS = 256
+
+
+def _hist_inputs(n, f, TB, seed):
+    rng = np.random.default_rng(seed)
+    fp = (f + 3) // 4 * 4
+    codes = np.zeros((n, fp), dtype=np.uint8)
+    codes[:, :f] = rng.integers(0, 256, (n, f), dtype=np.uint8)
+    codes[:256, 0] = np.arange(256, dtype=np.uint8)   # every code occurs
+    y = rng.integers(-4, 5, n).astype(np.float32)
+    row_w = (rng.integers(1, 9, n) / 4.0).astype(np.float32)
+    mult = rng.integers(0, 4, (TB, n), dtype=np.uint8)
+    si = np.stack([rng.permutation(n) for _ in range(TB)]).astype(np.int32)
+    return codes, y, row_w, mult, si
+
+
+def _chunks(segments):
+    """[(slot, tree, start, count)] -> chunk table split at CHUNK_ROWS."""
+    out = []
+    for slot, tree, start, count in segments:
+        for off in range(0, count, CHUNK_ROWS):
+            out.append((slot, tree, start + off,
+                        min(CHUNK_ROWS, count - off)))
+    return np.asarray(out, dtype=np.int32)
+
+
+def _hist_ref(codes, y, row_w, mult, si, segments, f, n_slots):
+    """fp64 host reference of (W, Wy, Wyy, C) per (slot, feature, bin)."""
+    ref = np.zeros((n_slots, f, NBINS, 4), dtype=np.float64)
+    for slot, tree, start, count in segments:
+        rows = si[tree, start:start + count].astype(np.int64)
+        m = mult[tree, rows].astype(np.float64)
+        w = m * row_w[rows].astype(np.float64)
+        yv = y[rows].astype(np.float64)
+        for j in range(f):
+            b = codes[rows, j].astype(np.int64)
+            for s, v in enumerate((w, w * yv, w * yv * yv, m)):
+                ref[slot, j, :, s] += np.bincount(b, weights=v,
+                                                  minlength=NBINS)
+    return ref
+
+
+def _run_hist_w(codes, y, row_w, mult, si, segments, f, n_slots, fg):
+    ext = require_hip()
+    dev = "cuda"
+    n = len(codes)
+    hist = torch.zeros(n_slots, f, NBINS, 4, dtype=torch.float32,
+                       device=dev)
+    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)
+    ext.tree_hist_w(t(codes), t(y), t(row_w), t(mult), t(si),
+                    t(_chunks(segments)), hist, n, f, NBINS, fg)
+    torch.cuda.synchronize()
+    return hist.cpu().numpy()
+
+
+def _assert_bit_equal(got, ref):
+    ref32 = ref.astype(np.float32)
+    assert np.array_equal(ref32.astype(np.float64), ref)  # representable
+    assert np.array_equal(got.view(np.uint32), ref32.view(np.uint32))
+
+
+def test_tree_hist_w_large_bit_equal():
+    n, f, TB, fg = 33_000, 21, 2, 16
+    codes, y, row_w, mult, si = _hist_inputs(n, f, TB, seed=0)
+    assert set(np.unique(codes[:, :f])) == set(range(256))
+    segments = [(0, 0, 0, n), (1, 1, 0, n)]   # each root spans two chunks
+    assert len(_chunks(segments)) == 4
+    got = _run_hist_w(codes, y, row_w, mult, si, segments, f, TB, fg)
+    ref = _hist_ref(codes, y, row_w, mult, si, segments, f, TB)
+    assert ref.max() < 2 ** 22
+    _assert_bit_equal(got, ref)
+    # the count slot is the sum of the uint8 multiplicities
+    assert got[0, 0, :, 3].sum() == mult[0].sum()
+    assert not np.array_equal(got[0], got[1])
+
+
+# f=3: fp=4, one group with a 3-feature tail of the uchar4 load;
+# f=7 with fg=3: groups at g0 = 3 and 6 take the byte-load path
+@pytest.mark.parametrize("f,fg", [(3, 3), (7, 3)])
+def test_tree_hist_w_small_segments_bit_equal(f, fg):
+    sizes = [1, 63, 64, 257, 1000]
+    n = sum(sizes)
+    codes, y, row_w, mult, si = _hist_inputs(n, f, 1, seed=1)
+    starts = np.cumsum([0] + sizes[:-1])
+    segments = [(k, 0, int(starts[k]), sizes[k]) for k in range(5)]
+    got = _run_hist_w(codes, y, row_w, mult, si, segments, f, 5, fg)
+    ref = _hist_ref(codes, y, row_w, mult, si, segments, f, 5)
+    _assert_bit_equal(got, ref)
+
+
+def test_tree_hist_w_rejects_bad_row_w():
+    n, f = 300, 4
+    codes, y, row_w, mult, si = _hist_inputs(n, f, 1, seed=2)
+    seg = [(0, 0, 0, n)]
+    with pytest.raises(RuntimeError, match="row_w"):
+        _run_hist_w(codes, y, row_w[:-1], mult, si, seg, f, 1, 4)
+    with pytest.raises(RuntimeError, match="row_w"):
+        _run_hist_w(codes, y, row_w.astype(np.float64), mult, si, seg, f,
+                    1, 4)
+
+
+# ---------------------------------------------------------------------- #
+# split rule on counts
+# ---------------------------------------------------------------------- #
+def _split(hist_np, S, min_leaf, cnt_stat, counted_binding=True):
+    ext = require_hip()
+    dev = "cuda"
+    NF, f, nbins, _ = hist_np.shape
+    hist = torch.as_tensor(np.ascontiguousarray(hist_np, dtype=np.float32),
+                           device=dev)
+    seed = torch.zeros(NF, dtype=torch.int32, device=dev)
+    oi = lambda: torch.full((NF,), -7, dtype=torch.int32, device=dev)
+    of = lambda *s: torch.zeros(*s, dtype=torch.float32, device=dev)
+    out = (oi(), oi(), of(NF), of(NF), of(NF), of(NF, S), of(NF, S))
+    CRIT_MSE = 2
+    args = (hist, seed, f, nbins, S, 0, CRIT_MSE, f, 0, float(min_leaf))
+    if counted_binding:
+        ext.tree_split_w(*args, *out, cnt_stat)
+    else:
+        ext.tree_split(*args, *out)
+    torch.cuda.synchronize()
+    return [o.cpu().numpy() for o in out]
+
+
+def test_tree_split_w_min_leaf_counts_rows():
+    nbins = 4
+    H = np.zeros((2, 1, nbins, 4))
+    # node A: 5 rows of weight 0.25 (y=4) | 10 rows of weight 1 (y=0)
+    H[0, 0, 0] = (1.25, 5.0, 20.0, 5.0)
+    H[0, 0, 1] = (10.0, 0.0, 0.0, 10.0)
+    # node B: 2 rows of weight 2 (y=4) | 3 rows w 1 (y=1) | 10 rows w 1
+    # (y=-1); cutting after bin 0 has the higher gain
+    H[1, 0, 0] = (4.0, 16.0, 64.0, 2.0)
+    H[1, 0, 1] = (3.0, 3.0, 3.0, 3.0)
+    H[1, 0, 2] = (10.0, -10.0, 10.0, 10.0)
+
+    def proxy(l, p):   # variance-reduction proxy of a cut
+        r = p - l
+        return l[1] ** 2 / l[0] + r[1] ** 2 / r[0]
+
+    pB = H[1, 0].sum(axis=0)
+    assert proxy(H[1, 0, 0], pB) > proxy(H[1, 0, :2].sum(axis=0), pB)
+
+    feat, bin_, wl, gain, imp, stats, lstats = _split(H, 4, 3, cnt_stat=3)
+    # A: left W=1.25 but C=5 >= 3 -> accepted
+    assert (feat[0], bin_[0]) == (0, 0)
+    assert wl[0] == 1.25
+    np.testing.assert_array_equal(lstats[0], H[0, 0, 0])
+    # B: the higher-gain cut has C=2 < 3 -> rejected; the next one wins
+    assert (feat[1], bin_[1]) == (0, 1)
+    assert wl[1] == 7.0
+    np.testing.assert_array_equal(lstats[1], H[1, 0, :2].sum(axis=0))
+    np.testing.assert_array_equal(stats, H[:, 0].sum(axis=1))
+    assert (gain > 0).all()
+
+    # today's rule on the 3-slot copy: the weight sums are compared
+    H3 = np.ascontiguousarray(H[..., :3])
+    new = _split(H3, 3, 3, cnt_stat=-1)
+    old = _split(H3, 3, 3, cnt_stat=None, counted_binding=False)
+    for a, b in zip(new, old):
+        np.testing.assert_array_equal(a, b)
+    feat3, bin3 = new[0], new[1]
+    assert feat3[0] == -1               # A: wl = 1.25 < 3
+    assert (feat3[1], bin3[1]) == (0, 0)  # B: wl = 4 >= 3, higher gain
+
+
+# ---------------------------------------------------------------------- #
+# builder
+# ---------------------------------------------------------------------- #
+def _same_structure(a, b):
+    for name in ("feature", "threshold", "left", "right"):
+        np.testing.assert_array_equal(getattr(a, name), getattr(b, name))
+
+
+def test_unit_row_weight_builds_todays_trees():
+    rng = np.random.default_rng(3)
+    n, f = 2500, 8
+    X = rng.standard_normal((n, f)).astype(np.float32)
+    y = np.clip(np.round(X @ rng.standard_normal(f)), -4, 4).astype(
+        np.float32)
+    kw = dict(max_depth=6, bootstrap=False, engine="hip")
+    ds0 = BinnedDataset(X, y, "cuda", is_cls=False)
+    ds1 = BinnedDataset(X, y, "cuda", is_cls=False,
+                        row_weight=np.ones(n, dtype=np.float32))
+    assert (ds0.S, ds1.S) == (3, 4)
+    t0 = ForestBuilder(ds0, "squared_error", **kw).build([3])[0]
+    t1 = ForestBuilder(ds1, "squared_error", **kw).build([3])[0]
+    assert len(t0.feature) > 15
+    _same_structure(t0, t1)
+    np.testing.assert_array_equal(t0.value, t1.value)
+
+
+def test_row_weight_rejected_for_classification():
+    X = np.zeros((8, 2), dtype=np.float32)
+    with pytest.raises(ValueError, match="regression"):
+        BinnedDataset(X, np.arange(8) % 2, "cuda", is_cls=True,
+                      row_weight=np.ones(8))
+
+
+def test_hip_builder_row_weight_matches_eager(monkeypatch):
+    monkeypatch.setenv("SKDIST_AMD_ALLOW_EAGER", "1")
+    rng = np.random.default_rng(5)
+    X = rng.standard_normal((2500, 8)).astype(np.float32)
+    yr = (X @ rng.standard_normal(8)).astype(np.float32)
+    rw = rng.uniform(0.1, 5, 2500).astype(np.float32)
+    ds = BinnedDataset(X, yr, "cuda", is_cls=False, row_weight=rw)
+    kw = dict(max_depth=7, max_features=1.0, bootstrap=True, tree_batch=2)
+    th = ForestBuilder(ds, "squared_error", engine="hip", **kw).build([9])
+    te = ForestBuilder(ds, "squared_error", engine="eager",
+                       **kw).build([9])
+    pa, pb = th[0].predict(X), te[0].predict(X)
+    # fp32 atomic-order rounding can flip near-tie splits
+    assert np.corrcoef(pa, pb)[0, 1] > 0.99
+    # the weights matter: the unweighted tree is a different one
+    ds0 = BinnedDataset(X, yr, "cuda", is_cls=False)
+    t0 = ForestBuilder(ds0, "squared_error", engine="hip", **kw).build([9])
+    assert not np.array_equal(t0[0].predict(X), pa)
+
+
+# ---------------------------------------------------------------------- #
+# end to end on the device
+# ---------------------------------------------------------------------- #
+def _label(X, noise):
+    return (2 * X[:, 0] - 2.8 + 0.5 * noise > 0).astype(np.int64)
+
+
+def _imbalanced():
+    rng = np.random.default_rng(0)
+    X = rng.standard_normal((3000, 8)).astype(np.float32)
+    y = _label(X, rng.standard_normal(3000))
+    Xh = rng.standard_normal((4000, 8)).astype(np.float32)
+    yh = _label(Xh, rng.standard_normal(4000))
+    return X, y, Xh, yh
+
+
+def test_device_weighted_classifier_matches_sklearn_recall():
+    from sklearn.ensemble import GradientBoostingClassifier as SkGBC
+    from sklearn.metrics import recall_score
+    from sklearn.utils.class_weight import compute_sample_weight
+
+    X, y, Xh, yh = _imbalanced()
+    sw = compute_sample_weight("balanced", y)
+    kw = dict(n_estimators=30, random_state=0)
+    ours = HistGradientBoostingClassifier(**kw).fit(X, y, sample_weight=sw)
+    unw = HistGradientBoostingClassifier(**kw).fit(X, y)
+    sk = SkGBC(**kw).fit(X, y, sample_weight=sw)
+    r_ours = recall_score(yh, ours.predict(Xh))
+    r_sk = recall_score(yh, sk.predict(Xh))
+    r_unw = recall_score(yh, unw.predict(Xh))
+    print("recall ours", r_ours, "sklearn", r_sk, "ours unweighted", r_unw)
+    assert r_ours >= r_sk - 0.03, (r_ours, r_sk)
+    assert r_ours >= r_unw + 0.05, (r_ours, r_unw)
+
+
+def test_device_weighted_regressor_matches_sklearn_r2():
+    from sklearn.ensemble import GradientBoostingRegressor as SkGBR
+    from sklearn.metrics import r2_score
+
+    X = _imbalanced()[0]
+    n = len(X)
+    half = np.arange(n) < n // 2
+    t = np.where(half, 2 * X[:, 0] + np.abs(X[:, 1]), -X[:, 0] + X[:, 2])
+    sw = np.where(half, 8.0, 0.125)
+    kw = dict(n_estimators=40, random_state=0)
+    ours = HistGradientBoostingRegressor(**kw).fit(X, t, sample_weight=sw)
+    sk = SkGBR(**kw).fit(X, t, sample_weight=sw)
+    r_ours = r2_score(t, ours.predict(X), sample_weight=sw)
+    r_sk = r2_score(t, sk.predict(X), sample_weight=sw)
+    print("weighted R2 ours", r_ours, "sklearn", r_sk)
+    assert r_ours >= r_sk - 0.03, (r_ours, r_sk)
+
+
+def _sparse_informative(m, seed):
+    rng = np.random.default_rng(seed)
+    X = rng.standard_normal((m, 8)).astype(np.float32)
+    X[np.abs(X) < 0.6] = 0.0
+    w = np.array([2.0, 1.5, -1.2, 1.0, -0.8, 0.7, -0.6, 0.5])
+    y = (X @ w + 0.3 * rng.standard_normal(m) > 2.5).astype(np.int64)
+    return X, y
+
+
+def test_device_csr_with_weights_matches_dense():
+    """Device fit from CSR against the device fit from the dense array,
+    same weights: within 1e-5 on at least 99% of the rows.
+
+    The two fits see the same codes and differ only in the arrival order
+    of the fp32 atomics, which moves a gain by about 1e-7 of the node's
+    impurity.  That decides a split only where candidates are tied at
+    that level, which is the rule among pure-noise features (their gains
+    are all ~impurity/n apart, and the f32 ``E[y^2] - E[y]^2`` form
+    cancels).  So the data here give EVERY feature signal and the trees
+    stay at depth 2 for 6 rounds: the CSR plumbing (resident CSR leaf
+    assignment, row weights, CSR predict) is exercised in full, and a
+    plumbing error would move most rows, not 1%.  On the imbalanced data
+    set (7 of 8 features pure noise, depth 3, 12 rounds) two runs of
+    this comparison gave 100% and 95.5% of the rows within 1e-5."""
+    import scipy.sparse as sp
+    from sklearn.utils.class_weight import compute_sample_weight
+
+    Xs, y = _sparse_informative(3000, 3)
+    Xhs, _ = _sparse_informative(4000, 4)
+    sw = compute_sample_weight("balanced", y)
+    kw = dict(n_estimators=6, max_depth=2, random_state=0)
+    a = HistGradientBoostingClassifier(**kw).fit(Xs, y, sample_weight=sw)
+    b = HistGradientBoostingClassifier(**kw).fit(
+        sp.csr_matrix(Xs), y, sample_weight=sw)
+    pa = a.predict_proba(Xhs)
+    pb = b.predict_proba(sp.csr_matrix(Xhs))
+    # fp32 atomic order may flip a near-tie split
+    close = np.abs(pa - pb).max(axis=1) <= 1e-5
+    print("rows within 1e-5:", close.mean())
+    assert close.mean() >= 0.99, close.mean()

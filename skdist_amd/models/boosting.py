@@ -58,7 +58,8 @@ import torch
 from sklearn.base import BaseEstimator, ClassifierMixin, RegressorMixin
 
 from ._sgd import as_dense_f32
-from .forest import BinnedDataset, ForestBuilder, HistTree, canonical_csr
+from .forest import (BinnedDataset, ForestBuilder, HistTree, canonical_csr,
+                     forest_walk)
 
 
 def _leaf_rows(tree, X):
@@ -73,8 +74,8 @@ def _leaf_value_rows(tree, X, Xdev, dev):
     if Xdev is None:
         return torch.as_tensor(_leaf_rows(tree, X), dtype=torch.int64,
                                device=dev)
-    csr = isinstance(Xdev, tuple)   # resident (indptr, indices, data)
-    n = len(Xdev[0]) - 1 if csr else len(Xdev)
+    # a resident CSR X is the tuple (indptr, indices, data)
+    n = len(Xdev[0]) - 1 if isinstance(Xdev, tuple) else len(Xdev)
     from ..ops import require_hip
 
     ext = require_hip()
@@ -86,10 +87,7 @@ def _leaf_value_rows(tree, X, Xdev, dev):
     right = as_t(tree.right, torch.int32)
     roots = torch.zeros(1, dtype=torch.int32, device=dev)
     out = torch.empty(n, 1, dtype=torch.int32, device=dev)
-    if csr:
-        ext.forest_apply_csr(*Xdev, feat, thr, left, right, roots, out)
-    else:
-        ext.forest_apply(Xdev, feat, thr, left, right, roots, out)
+    forest_walk(ext, "apply", Xdev, feat, thr, left, right, roots, out)
     return left.index_select(
         0, out[:, 0].to(torch.int64)).to(torch.int64)
 

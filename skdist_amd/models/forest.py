@@ -591,7 +591,12 @@ class ForestBuilder:
                 "production path)")
         self.engine = engine
         # index of the row-count stat (datasets with a row-weight plane)
-        self.cnt_stat = 3 if getattr(ds, "row_w", None) is not None else -1
+        self.cnt_stat = 3 if ds.row_w is not None else -1
+        # scale of the uint8 weight plane and the min_samples thresholds
+        # in that scale (make_weights / _build_batch set them per batch)
+        self._w_scale = 1.0
+        self._mss_eff = self.mss
+        self._msl_eff = self.msl
         # features per LDS group for the hist kernel
         per_feat = ds.nbins * ds.S * 4
         fg = max(1, min(ds.f, self.LDS_BUDGET_BYTES // per_feat))
@@ -656,9 +661,8 @@ class ForestBuilder:
         weights = self.make_weights(seeds, sample_weight)
         # weighted-count thresholds live in the (possibly quantized)
         # weight-plane scale
-        ws = getattr(self, "_w_scale", 1.0)
-        self._mss_eff = self.mss * ws
-        self._msl_eff = self.msl * ws
+        self._mss_eff = self.mss * self._w_scale
+        self._msl_eff = self.msl * self._w_scale
         si_a, counts = self._initial_sample_idx(weights)
         si_b = torch.empty_like(si_a)
 
@@ -966,18 +970,12 @@ class ForestBuilder:
             return
         chunks_np = self._chunk_table(tree, start, count, slot)
         chunks = torch.as_tensor(chunks_np, device=dev)
-        if self.cnt_stat >= 0:
-            self._ext.tree_hist_w(
-                ds.codes, ds.y_f, ds.row_w, weights, si, chunks, hist,
-                ds.n, ds.f, ds.nbins, self.fg)
-            return
+        absent = torch.empty(0, device=dev)   # the binding's "not given"
         self._ext.tree_hist(
-            ds.codes, ds.y_int if ds.is_cls else torch.empty(
-                0, dtype=torch.int32, device=dev),
-            ds.y_f if not ds.is_cls else torch.empty(
-                0, dtype=torch.float32, device=dev),
-            weights, si, chunks, hist, ds.n, ds.f, ds.nbins, ds.S,
-            int(ds.is_cls), self.fg)
+            ds.codes, ds.y_int if ds.is_cls else absent,
+            absent if ds.is_cls else ds.y_f,
+            absent if ds.row_w is None else ds.row_w,
+            weights, si, chunks, hist, ds.n, ds.f, ds.nbins, self.fg)
 
     def _run_split_kernel(self, hist, node_seed, NF):
         ds = self.ds
@@ -995,20 +993,11 @@ class ForestBuilder:
         out_imp = fbuf[2 * NF: 3 * NF]
         out_stats = fbuf[3 * NF: (3 + S) * NF].view(NF, S)
         out_lstats = fbuf[(3 + S) * NF:].view(NF, S)
-        if self.cnt_stat >= 0:
-            self._ext.tree_split_w(
-                hist, seed_t, ds.f, ds.nbins, S, int(ds.is_cls), self.crit,
-                self.m_features, int(self.extra_mode),
-                float(getattr(self, "_msl_eff", self.msl)),
-                out_feat, out_bin, out_wl, out_gain, out_imp, out_stats,
-                out_lstats, self.cnt_stat)
-        else:
-            self._ext.tree_split(
-                hist, seed_t, ds.f, ds.nbins, S, int(ds.is_cls), self.crit,
-                self.m_features, int(self.extra_mode),
-                float(getattr(self, "_msl_eff", self.msl)),
-                out_feat, out_bin, out_wl, out_gain, out_imp, out_stats,
-                out_lstats)
+        self._ext.tree_split(
+            hist, seed_t, ds.f, ds.nbins, S, int(ds.is_cls), self.crit,
+            self.m_features, int(self.extra_mode), self._msl_eff,
+            out_feat, out_bin, out_wl, out_gain, out_imp, out_stats,
+            out_lstats, self.cnt_stat)
         ih = ibuf.cpu().numpy()
         fh = fbuf.cpu().numpy().astype(np.float64)
         return (ih[:NF].astype(np.int64),
@@ -1138,7 +1127,7 @@ class ForestBuilder:
                     (parent[2] - cum[:, :, 2]) / wr - mr * mr, 0.0)
         with np.errstate(invalid="ignore"):
             gain = imp_p - (wl * imp_l + wr * imp_r) / max(wp, 1e-30)
-        msl = getattr(self, "_msl_eff", self.msl)
+        msl = self._msl_eff
         if self.cnt_stat >= 0:
             # k_tree_split_w: min-leaf on row counts, weight on both sides
             cl = cum[:, :, self.cnt_stat]
@@ -1242,6 +1231,16 @@ def _allow_eager():
 # flattened device forest (batched inference kernel)
 # --------------------------------------------------------------------- #
 
+def forest_walk(ext, op, xdev, *args):
+    """The one entry to the inference kernels: ``op`` is "predict" or
+    "apply", ``xdev`` a device f32 ``[rows, f]`` block or a device CSR
+    ``(indptr, indices, data)``; ``args`` go on to the binding."""
+    if isinstance(xdev, tuple):
+        getattr(ext, f"forest_{op}_csr")(*xdev, *args)
+    else:
+        getattr(ext, f"forest_{op}")(xdev, *args)
+
+
 class FlatForest:
     """A list of HistTrees flattened into device arrays for the batched
     inference kernels (k_forest_predict / k_forest_apply,
@@ -1291,66 +1290,43 @@ class FlatForest:
         self.classes_ = trees[0].classes_
         self.n_features = trees[0].n_features_in_
 
-    def predict_value(self, X, chunk_rows=1 << 22):
-        """Mean leaf payload over trees: [rows, vs] numpy."""
-        import scipy.sparse as sp
-
-        if sp.issparse(X):
-            return self._predict_value_csr(X, chunk_rows)
-        X = np.ascontiguousarray(X, dtype=np.float32)
-        outs = []
-        for lo in range(0, len(X), chunk_rows):
-            xb = torch.as_tensor(
-                X[lo: lo + chunk_rows], device=self.device)
-            out = torch.empty(len(xb), self.vs, dtype=torch.float32,
-                              device=self.device)
-            self._ext.forest_predict(xb, self.feat, self.thr, self.left,
-                                     self.right, self.roots, self.values,
-                                     out)
-            outs.append(out.cpu().numpy())
-        return np.concatenate(outs, axis=0)
-
     # stored entries uploaded per CSR chunk (12 bytes each on device)
     CSR_CHUNK_NNZ = 1 << 27
 
-    def _csr_chunks(self, X, chunk_rows):
-        """Canonicalise a scipy-sparse X and yield per-chunk device
-        ``(rows, indptr, indices, data)`` with ``indptr`` rebased to 0.
-        Chunks are bounded by a row count and a stored-entry count; X is
-        never densified."""
+    def _chunks(self, X, chunk_rows):
+        """Yield ``(rows, xdev)`` per chunk of X for ``forest_walk``: a
+        device f32 block of an array, or of a scipy-sparse X (canonical
+        copy, never densified) a device CSR triple with ``indptr`` rebased
+        to 0, bounded by a row count and a stored-entry count."""
+        import scipy.sparse as sp
+
+        dev = self.device
+        if not sp.issparse(X):
+            X = np.ascontiguousarray(X, dtype=np.float32)
+            for lo in range(0, len(X), chunk_rows):
+                xb = torch.as_tensor(X[lo: lo + chunk_rows], device=dev)
+                yield len(xb), xb
+            return
         C = canonical_csr(X, self.n_features)
-        for lo, hi in _csr_row_chunks(C.indptr, chunk_rows,
-                                      self.CSR_CHUNK_NNZ):
+        # a sparse X without rows is one empty chunk -> [0, width] output
+        for lo, hi in list(_csr_row_chunks(
+                C.indptr, chunk_rows, self.CSR_CHUNK_NNZ)) or [(0, 0)]:
             a, b = int(C.indptr[lo]), int(C.indptr[hi])
-            dev = self.device
-            yield (
-                hi - lo,
+            yield hi - lo, (
                 torch.as_tensor(C.indptr[lo: hi + 1] - a, device=dev),
                 torch.as_tensor(C.indices[a:b], device=dev),
                 torch.as_tensor(C.data[a:b], device=dev),
             )
 
-    def _predict_value_csr(self, X, chunk_rows):
-        outs = [np.zeros((0, self.vs), dtype=np.float32)]
-        for rows, indptr, indices, data in self._csr_chunks(X, chunk_rows):
+    def predict_value(self, X, chunk_rows=1 << 22):
+        """Mean leaf payload over trees: [rows, vs] numpy."""
+        outs = []
+        for rows, xdev in self._chunks(X, chunk_rows):
             out = torch.empty(rows, self.vs, dtype=torch.float32,
                               device=self.device)
-            self._ext.forest_predict_csr(
-                indptr, indices, data, self.feat, self.thr, self.left,
-                self.right, self.roots, self.values, out)
+            forest_walk(self._ext, "predict", xdev, self.feat, self.thr,
+                        self.left, self.right, self.roots, self.values, out)
             outs.append(out.cpu().numpy())
-        return np.concatenate(outs, axis=0)
-
-    def _apply_csr(self, X, chunk_rows):
-        roots_np = self.roots.cpu().numpy().astype(np.int64)
-        outs = [np.zeros((0, self.n_trees), dtype=np.int64)]
-        for rows, indptr, indices, data in self._csr_chunks(X, chunk_rows):
-            out = torch.empty(rows, self.n_trees, dtype=torch.int32,
-                              device=self.device)
-            self._ext.forest_apply_csr(
-                indptr, indices, data, self.feat, self.thr, self.left,
-                self.right, self.roots, out)
-            outs.append(out.cpu().numpy() - roots_np[None, :])
         return np.concatenate(outs, axis=0)
 
     def predict_proba(self, X):
@@ -1365,20 +1341,13 @@ class FlatForest:
     def apply(self, X, chunk_rows=1 << 21):
         """Leaf node id per (row, tree): [rows, n_trees] int32 — ids are
         tree-local (matching HistTree.apply) for embedding parity."""
-        import scipy.sparse as sp
-
-        if sp.issparse(X):
-            return self._apply_csr(X, chunk_rows)
-        X = np.ascontiguousarray(X, dtype=np.float32)
         roots_np = self.roots.cpu().numpy().astype(np.int64)
         outs = []
-        for lo in range(0, len(X), chunk_rows):
-            xb = torch.as_tensor(
-                X[lo: lo + chunk_rows], device=self.device)
-            out = torch.empty(len(xb), self.n_trees, dtype=torch.int32,
+        for rows, xdev in self._chunks(X, chunk_rows):
+            out = torch.empty(rows, self.n_trees, dtype=torch.int32,
                               device=self.device)
-            self._ext.forest_apply(xb, self.feat, self.thr, self.left,
-                                   self.right, self.roots, out)
+            forest_walk(self._ext, "apply", xdev, self.feat, self.thr,
+                        self.left, self.right, self.roots, out)
             outs.append(out.cpu().numpy() - roots_np[None, :])
         return np.concatenate(outs, axis=0)
 

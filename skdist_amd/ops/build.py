@@ -58,12 +58,13 @@ def build(verbose=True):
         "hipcc", f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
         "-Wall", "-Wno-unused-function",
     ]
+    headers = [os.path.join(CSRC, h) for h in ("common.h", "tree_api.h")]
     for src in KERNEL_SOURCES:
         path = os.path.join(CSRC, src)
         if not os.path.exists(path):
             continue
         obj = os.path.join(CSRC, src.rsplit(".", 1)[0] + ".o")
-        if not _stale(obj, [path, os.path.join(CSRC, "common.h")]):
+        if not _stale(obj, [path] + headers):
             objs.append(obj)
             continue
         _run(common + ["-c", path, "-o", obj])
@@ -71,7 +72,7 @@ def build(verbose=True):
     for src in BINDING_SOURCES:
         path = os.path.join(CSRC, src)
         obj = os.path.join(CSRC, src.rsplit(".", 1)[0] + ".o")
-        if _stale(obj, [path]):
+        if _stale(obj, [path] + headers):
             _run(common + includes + defines + ["-fno-gpu-rdc", "-c", path,
                                                 "-o", obj])
         objs.append(obj)

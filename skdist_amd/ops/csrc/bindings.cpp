@@ -5,6 +5,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include "tree_api.h"
+
 extern "C" hipError_t skdist_sgd_step(
     const void* Xs, const void* XsT, const void* WbfT_in,
     void* GT, void* W, void* V, void* WbfT, void* partial,
@@ -385,62 +387,10 @@ void sp_renorm(torch::Tensor W, torch::Tensor s) {
 }  // namespace
 
 // ------------------------------------------------------------------ //
-// histogram tree builder (tree_kernels.hip)
+// tree family (tree_kernels.hip, predict_kernels.hip: launchers declared
+// in tree_api.h), scoring, standardize and hashing
 // ------------------------------------------------------------------ //
 
-extern "C" hipError_t skdist_tree_hist(
-    const void* codes, const void* y_int, const void* y_f,
-    const void* weights, const void* sample_idx, const void* chunks,
-    void* hist, long long n, int f, int fp, int nbins, int S, int is_cls,
-    int fg, int n_chunks, hipStream_t stream);
-extern "C" hipError_t skdist_tree_split(
-    const void* hist, const void* node_seed, int n_frontier, int f,
-    int nbins, int S, int is_cls, int crit, int m_features, int extra_mode,
-    float min_leaf_w, void* out_feat, void* out_bin, void* out_wl,
-    void* out_gain, void* out_imp, void* out_stats, void* out_lstats,
-    hipStream_t stream);
-extern "C" hipError_t skdist_tree_hist_w(
-    const void* codes, const void* y_f, const void* row_w,
-    const void* weights, const void* sample_idx, const void* chunks,
-    void* hist, long long n, int f, int fp, int nbins, int fg,
-    int n_chunks, hipStream_t stream);
-extern "C" hipError_t skdist_tree_split_w(
-    const void* hist, const void* node_seed, int n_frontier, int f,
-    int nbins, int S, int is_cls, int crit, int m_features, int extra_mode,
-    float min_leaf, int cnt_stat, void* out_feat, void* out_bin,
-    void* out_wl, void* out_gain, void* out_imp, void* out_stats,
-    void* out_lstats, hipStream_t stream);
-extern "C" hipError_t skdist_part_count(
-    const void* codes, const void* sample_idx, const void* chunks,
-    const void* split_feat, const void* split_bin, long long n, int fp,
-    int n_chunks, void* out_counts, hipStream_t stream);
-extern "C" hipError_t skdist_part_scatter(
-    const void* codes, const void* sample_idx_in, const void* chunks,
-    const void* split_feat, const void* split_bin, const void* left_base,
-    const void* right_base, long long n, int fp, int n_chunks,
-    void* sample_idx_out, hipStream_t stream);
-extern "C" hipError_t skdist_forest_predict(
-    const void* X, const void* feat, const void* thr, const void* left,
-    const void* right, const void* roots, const void* values, void* out,
-    long long rows, int f, int n_trees, int vs, hipStream_t stream);
-extern "C" hipError_t skdist_forest_apply(
-    const void* X, const void* feat, const void* thr, const void* left,
-    const void* right, const void* roots, void* out_leaf, long long rows,
-    int f, int n_trees, hipStream_t stream);
-extern "C" hipError_t skdist_forest_predict_csr(
-    const void* indptr, const void* indices, const void* data,
-    const void* feat, const void* thr, const void* left, const void* right,
-    const void* roots, const void* values, void* out, long long rows,
-    long long nnz, int n_trees, int vs, hipStream_t stream);
-extern "C" hipError_t skdist_forest_apply_csr(
-    const void* indptr, const void* indices, const void* data,
-    const void* feat, const void* thr, const void* left, const void* right,
-    const void* roots, void* out_leaf, long long rows, long long nnz,
-    int n_trees, hipStream_t stream);
-extern "C" hipError_t skdist_bin_csr(
-    const void* indptr, const void* indices, const void* data,
-    const void* edges, const void* zc4, void* codes, long long n,
-    long long nnz, int f, int fp, int nedges, hipStream_t stream);
 extern "C" hipError_t skdist_score(
     const void* Xf, const void* WbfT, const void* yf, void* out,
     long long m_pad, int fa, int ncols_pad, int mode,
@@ -460,151 +410,203 @@ extern "C" hipError_t skdist_hash_vectorize_utf8(
 
 namespace {
 
-void tree_hist(torch::Tensor codes, torch::Tensor y_int, torch::Tensor y_f,
-               torch::Tensor weights, torch::Tensor sample_idx,
-               torch::Tensor chunks, torch::Tensor hist, int64_t n,
-               int64_t f, int64_t nbins, int64_t S, int64_t is_cls,
-               int64_t fg) {
-    const int64_t fp = codes.size(1);
-    for (auto* t : {&codes, &weights, &sample_idx, &chunks, &hist}) {
-        CHECK_DEV(*t);
-        CHECK_CONT(*t);
-    }
-    TORCH_CHECK(codes.scalar_type() == torch::kUInt8, "codes must be u8");
-    TORCH_CHECK(chunks.size(1) == 4, "chunks must be [n_chunks, 4]");
-    auto stream = c10::hip::getCurrentHIPStream().stream();
-    hipError_t err = skdist_tree_hist(
-        codes.data_ptr(), is_cls ? y_int.data_ptr() : nullptr,
-        is_cls ? nullptr : y_f.data_ptr(), weights.data_ptr(),
-        sample_idx.data_ptr(), chunks.data_ptr(), hist.data_ptr(), n,
-        (int)f, (int)fp, (int)nbins, (int)S, (int)is_cls, (int)fg,
-        (int)chunks.size(0), stream);
-    TORCH_CHECK(err == hipSuccess, "tree_hist: ", hipGetErrorString(err));
+// ---- argument checks of the tree bindings.  The launchers take void*, so
+// every tensor that reaches one is first pinned to the device, layout and
+// dtype its kernel reads; a binding launches nothing on empty work.
+void check_t(const torch::Tensor& t, torch::ScalarType dt,
+             const char* name) {
+    TORCH_CHECK(t.is_cuda(), name, " must be on the GPU");
+    TORCH_CHECK(t.is_contiguous(), name, " not contiguous");
+    TORCH_CHECK(t.scalar_type() == dt, name, " must be ", dt);
 }
 
+void check_vec(const torch::Tensor& t, torch::ScalarType dt, int64_t len,
+               const char* name) {
+    check_t(t, dt, name);
+    TORCH_CHECK(t.numel() == len, name, " must have ", len, " elements");
+}
+
+void check_2d(const torch::Tensor& t, torch::ScalarType dt, int64_t rows,
+              int64_t cols, const char* name) {
+    check_t(t, dt, name);
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == rows && t.size(1) == cols,
+                name, " must be [", rows, ", ", cols, "]");
+}
+
+// codes [n, fp] u8 with fp a multiple of 4 (uchar4 loads); returns fp
+int64_t check_codes(const torch::Tensor& codes, int64_t n) {
+    check_t(codes, torch::kUInt8, "codes");
+    TORCH_CHECK(codes.dim() == 2 && codes.size(0) == n &&
+                    codes.size(1) % 4 == 0 && codes.size(1) < (1LL << 31),
+                "codes must be [n, fp] with fp % 4 == 0");
+    return codes.size(1);
+}
+
+// chunk table [n_chunks, 4] i32; returns n_chunks
+int64_t check_chunks(const torch::Tensor& chunks) {
+    check_t(chunks, torch::kInt32, "chunks");
+    TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 4 &&
+                    chunks.size(0) < (1LL << 31),
+                "chunks must be [n_chunks, 4]");
+    return chunks.size(0);
+}
+
+// per-tree row plane [TB, n]; returns TB
+int64_t check_plane(const torch::Tensor& t, torch::ScalarType dt, int64_t n,
+                    const char* name) {
+    check_t(t, dt, name);
+    TORCH_CHECK(t.dim() == 2 && t.size(1) == n, name, " must be [TB, n]");
+    return t.size(0);
+}
+
+// CSR inputs shared by the sparse tree kernels: indptr int64 [rows+1],
+// indices int32 [nnz], data f32 [nnz], all contiguous on the GPU
+void check_csr(const torch::Tensor& indptr, const torch::Tensor& indices,
+               const torch::Tensor& data, int64_t rows) {
+    TORCH_CHECK(rows >= 0, "output must be 2-D");
+    check_vec(indptr, torch::kInt64, rows + 1, "indptr");
+    check_vec(indices, torch::kInt32, data.numel(), "indices");
+    check_t(data, torch::kFloat32, "data");
+    for (auto* t : {&indptr, &indices, &data})
+        TORCH_CHECK(t->dim() == 1, "CSR arrays must be 1-D");
+}
+
+// node arrays of a flattened forest: int32 / f32, equal lengths
+void check_nodes(const torch::Tensor& feat, const torch::Tensor& thr,
+                 const torch::Tensor& left, const torch::Tensor& right,
+                 const torch::Tensor& roots) {
+    const int64_t nodes = feat.numel();
+    check_t(feat, torch::kInt32, "feat");
+    check_vec(thr, torch::kFloat32, nodes, "thr");
+    check_vec(left, torch::kInt32, nodes, "left");
+    check_vec(right, torch::kInt32, nodes, "right");
+    check_t(roots, torch::kInt32, "roots");
+    TORCH_CHECK(roots.numel() >= 1 && nodes >= 1, "empty forest");
+    TORCH_CHECK(roots.numel() < (1LL << 31), "too many trees");
+}
+
+// leaf payloads values [n_values, vs] and out [rows, vs]; returns vs
+int64_t check_payload(const torch::Tensor& values, const torch::Tensor& out,
+                      int64_t rows) {
+    check_t(values, torch::kFloat32, "values");
+    TORCH_CHECK(values.dim() == 2 && values.size(1) >= 1 &&
+                    values.size(1) <= 32,
+                "values must be [n_values, vs] with vs <= 32 (MAXVS)");
+    check_2d(out, torch::kFloat32, rows, values.size(1), "out");
+    return values.size(1);
+}
+
+int64_t rows_of(const torch::Tensor& out) {
+    return out.dim() == 2 ? out.size(0) : -1;
+}
+
+// the current stream, and a launcher's verdict as an exception
+hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
+void launched(hipError_t err, const char* what) {
+    TORCH_CHECK(err == hipSuccess, what, ": ", hipGetErrorString(err));
+}
+
+// absent tensors (y_int / y_f / row_w) are passed empty
+void tree_hist(torch::Tensor codes, torch::Tensor y_int, torch::Tensor y_f,
+               torch::Tensor row_w, torch::Tensor weights,
+               torch::Tensor sample_idx, torch::Tensor chunks,
+               torch::Tensor hist, int64_t n, int64_t f, int64_t nbins,
+               int64_t fg) {
+    const int64_t fp = check_codes(codes, n);
+    const int64_t n_chunks = check_chunks(chunks);
+    const int64_t TB = check_plane(weights, torch::kUInt8, n, "weights");
+    TORCH_CHECK(check_plane(sample_idx, torch::kInt32, n, "sample_idx") ==
+                    TB, "weights and sample_idx differ in TB");
+    check_t(hist, torch::kFloat32, "hist");
+    TORCH_CHECK(f >= 1 && f <= fp, "f must be in [1, fp]");
+    TORCH_CHECK(nbins >= 1 && nbins <= 256, "nbins must be in [1, 256]");
+    TORCH_CHECK(hist.dim() == 4 && hist.size(1) == f &&
+                    hist.size(2) == nbins && hist.size(3) >= 1,
+                "hist must be [NF, f, nbins, S]");
+    const int64_t S = hist.size(3);
+    const bool cls = y_int.numel() > 0, has_w = row_w.numel() > 0;
+    TORCH_CHECK(cls != (y_f.numel() > 0),
+                "exactly one of y_int / y_f must be given");
+    if (cls) {
+        check_vec(y_int, torch::kInt32, n, "y_int");
+        TORCH_CHECK(!has_w, "row_w rides the regression stats (y_f) only");
+    } else {
+        check_vec(y_f, torch::kFloat32, n, "y_f");
+        if (has_w) check_vec(row_w, torch::kFloat32, n, "row_w");
+        TORCH_CHECK(S == (has_w ? 4 : 3),
+                    "hist must be [NF, f, nbins, 4] with row_w and "
+                    "[NF, f, nbins, 3] without");
+    }
+    TORCH_CHECK(fg >= 1 && fg <= fp && fg * nbins * S * 4 <= 64 * 1024,
+                "fg * nbins * S * 4 bytes must fit 64 KiB of LDS");
+    if (n_chunks == 0) return;
+    launched(skdist_tree_hist(
+        codes.data_ptr(), cls ? y_int.data_ptr() : nullptr,
+        cls ? nullptr : y_f.data_ptr(),
+        has_w ? row_w.data_ptr() : nullptr, weights.data_ptr(),
+        sample_idx.data_ptr(), chunks.data_ptr(), hist.data_ptr(), n,
+        (int)f, (int)fp, (int)nbins, (int)S, (int)fg, (int)n_chunks,
+        cur_stream()), "tree_hist");
+}
+
+// cnt_stat = -1: min-leaf on the weight sums; else on that (count) stat
 void tree_split(torch::Tensor hist, torch::Tensor node_seed, int64_t f,
                 int64_t nbins, int64_t S, int64_t is_cls, int64_t crit,
-                int64_t m_features, int64_t extra_mode, double min_leaf_w,
+                int64_t m_features, int64_t extra_mode, double min_leaf,
                 torch::Tensor out_feat, torch::Tensor out_bin,
                 torch::Tensor out_wl, torch::Tensor out_gain,
                 torch::Tensor out_imp, torch::Tensor out_stats,
-                torch::Tensor out_lstats) {
-    CHECK_DEV(hist);
-    CHECK_CONT(hist);
-    TORCH_CHECK(S <= 32, "tree_split supports <= 32 stats");
-    auto stream = c10::hip::getCurrentHIPStream().stream();
-    hipError_t err = skdist_tree_split(
-        hist.data_ptr(), node_seed.data_ptr(), (int)node_seed.size(0),
-        (int)f, (int)nbins, (int)S, (int)is_cls, (int)crit,
-        (int)m_features, (int)extra_mode, (float)min_leaf_w,
-        out_feat.data_ptr(), out_bin.data_ptr(), out_wl.data_ptr(),
-        out_gain.data_ptr(), out_imp.data_ptr(), out_stats.data_ptr(),
-        out_lstats.data_ptr(), stream);
-    TORCH_CHECK(err == hipSuccess, "tree_split: ", hipGetErrorString(err));
-}
-
-void tree_hist_w(torch::Tensor codes, torch::Tensor y_f, torch::Tensor row_w,
-                 torch::Tensor weights, torch::Tensor sample_idx,
-                 torch::Tensor chunks, torch::Tensor hist, int64_t n,
-                 int64_t f, int64_t nbins, int64_t fg) {
-    for (auto* t :
-         {&codes, &y_f, &row_w, &weights, &sample_idx, &chunks, &hist}) {
-        CHECK_DEV(*t);
-        CHECK_CONT(*t);
-    }
-    TORCH_CHECK(codes.scalar_type() == torch::kUInt8, "codes must be u8");
-    TORCH_CHECK(weights.scalar_type() == torch::kUInt8,
-                "weights must be u8");
-    TORCH_CHECK(y_f.scalar_type() == torch::kFloat32, "y_f must be f32");
-    TORCH_CHECK(row_w.scalar_type() == torch::kFloat32,
-                "row_w must be f32");
-    TORCH_CHECK(hist.scalar_type() == torch::kFloat32, "hist must be f32");
-    TORCH_CHECK(sample_idx.scalar_type() == torch::kInt32,
-                "sample_idx must be i32");
-    TORCH_CHECK(chunks.scalar_type() == torch::kInt32,
-                "chunks must be i32");
-    TORCH_CHECK(codes.dim() == 2 && codes.size(0) == n &&
-                    codes.size(1) % 4 == 0 && f >= 1 && f <= codes.size(1),
-                "codes must be [n, fp] with fp % 4 == 0 and f <= fp");
-    TORCH_CHECK(row_w.numel() == n, "row_w must have n elements");
-    TORCH_CHECK(y_f.numel() == n, "y_f must have n elements");
-    TORCH_CHECK(weights.dim() == 2 && weights.size(1) == n &&
-                    sample_idx.dim() == 2 && sample_idx.size(1) == n &&
-                    sample_idx.size(0) == weights.size(0),
-                "weights and sample_idx must be [TB, n]");
-    TORCH_CHECK(chunks.dim() == 2 && chunks.size(1) == 4,
-                "chunks must be [n_chunks, 4]");
-    TORCH_CHECK(nbins >= 1 && nbins <= 256, "nbins must be in [1, 256]");
-    TORCH_CHECK(hist.dim() == 4 && hist.size(1) == f &&
-                    hist.size(2) == nbins && hist.size(3) == 4,
-                "hist must be [NF, f, nbins, 4]");
-    TORCH_CHECK(fg >= 1 && fg * nbins * 16 <= 64 * 1024,
-                "fg * nbins * 16 bytes must fit 64 KiB of LDS");
-    const int64_t fp = codes.size(1);
-    auto stream = c10::hip::getCurrentHIPStream().stream();
-    hipError_t err = skdist_tree_hist_w(
-        codes.data_ptr(), y_f.data_ptr(), row_w.data_ptr(),
-        weights.data_ptr(), sample_idx.data_ptr(), chunks.data_ptr(),
-        hist.data_ptr(), n, (int)f, (int)fp, (int)nbins, (int)fg,
-        (int)chunks.size(0), stream);
-    TORCH_CHECK(err == hipSuccess, "tree_hist_w: ", hipGetErrorString(err));
-}
-
-void tree_split_w(torch::Tensor hist, torch::Tensor node_seed, int64_t f,
-                  int64_t nbins, int64_t S, int64_t is_cls, int64_t crit,
-                  int64_t m_features, int64_t extra_mode, double min_leaf,
-                  torch::Tensor out_feat, torch::Tensor out_bin,
-                  torch::Tensor out_wl, torch::Tensor out_gain,
-                  torch::Tensor out_imp, torch::Tensor out_stats,
-                  torch::Tensor out_lstats, int64_t cnt_stat) {
-    const int64_t NF = node_seed.size(0);
-    for (auto* t : {&hist, &node_seed, &out_feat, &out_bin, &out_wl,
-                    &out_gain, &out_imp, &out_stats, &out_lstats}) {
-        CHECK_DEV(*t);
-        CHECK_CONT(*t);
-    }
-    TORCH_CHECK(hist.scalar_type() == torch::kFloat32, "hist must be f32");
-    TORCH_CHECK(node_seed.scalar_type() == torch::kInt32,
-                "node_seed must be i32");
-    TORCH_CHECK(out_feat.scalar_type() == torch::kInt32 &&
-                    out_bin.scalar_type() == torch::kInt32,
-                "out_feat/out_bin must be i32");
-    for (auto* t : {&out_wl, &out_gain, &out_imp, &out_stats, &out_lstats})
-        TORCH_CHECK(t->scalar_type() == torch::kFloat32,
-                    "float outputs must be f32");
-    TORCH_CHECK(S >= 1 && S <= 32, "tree_split_w supports <= 32 stats");
+                torch::Tensor out_lstats, int64_t cnt_stat) {
+    const int64_t NF = node_seed.numel();
+    check_t(hist, torch::kFloat32, "hist");
+    check_t(node_seed, torch::kInt32, "node_seed");
+    check_vec(out_feat, torch::kInt32, NF, "out_feat");
+    check_vec(out_bin, torch::kInt32, NF, "out_bin");
+    check_vec(out_wl, torch::kFloat32, NF, "out_wl");
+    check_vec(out_gain, torch::kFloat32, NF, "out_gain");
+    check_vec(out_imp, torch::kFloat32, NF, "out_imp");
+    check_vec(out_stats, torch::kFloat32, NF * S, "out_stats");
+    check_vec(out_lstats, torch::kFloat32, NF * S, "out_lstats");
+    TORCH_CHECK(S >= 1 && S <= 32, "tree_split supports <= 32 stats");
     TORCH_CHECK(cnt_stat >= -1 && cnt_stat < S,
                 "cnt_stat must be -1 or a stat index");
-    TORCH_CHECK(hist.numel() >= NF * f * nbins * S, "hist too small");
-    TORCH_CHECK(out_feat.numel() >= NF && out_bin.numel() >= NF &&
-                    out_wl.numel() >= NF && out_gain.numel() >= NF &&
-                    out_imp.numel() >= NF && out_stats.numel() >= NF * S &&
-                    out_lstats.numel() >= NF * S,
-                "outputs too small for the frontier");
+    TORCH_CHECK(f >= 1 && nbins >= 1 && NF < (1LL << 31) &&
+                    hist.numel() >= NF * f * nbins * S, "hist too small");
     if (NF == 0) return;
-    auto stream = c10::hip::getCurrentHIPStream().stream();
-    hipError_t err = skdist_tree_split_w(
+    launched(skdist_tree_split(
         hist.data_ptr(), node_seed.data_ptr(), (int)NF, (int)f, (int)nbins,
         (int)S, (int)is_cls, (int)crit, (int)m_features, (int)extra_mode,
         (float)min_leaf, (int)cnt_stat, out_feat.data_ptr(),
         out_bin.data_ptr(), out_wl.data_ptr(), out_gain.data_ptr(),
         out_imp.data_ptr(), out_stats.data_ptr(), out_lstats.data_ptr(),
-        stream);
-    TORCH_CHECK(err == hipSuccess, "tree_split_w: ",
-                hipGetErrorString(err));
+        cur_stream()), "tree_split");
+}
+
+// split_feat / split_bin are indexed by the chunk table's part_slot
+int64_t check_part(const torch::Tensor& codes, const torch::Tensor& si,
+                   const torch::Tensor& chunks,
+                   const torch::Tensor& split_feat,
+                   const torch::Tensor& split_bin, int64_t n) {
+    check_codes(codes, n);
+    check_plane(si, torch::kInt32, n, "sample_idx");
+    check_t(split_feat, torch::kInt32, "split_feat");
+    check_vec(split_bin, torch::kInt32, split_feat.numel(), "split_bin");
+    return check_chunks(chunks);
 }
 
 void part_count(torch::Tensor codes, torch::Tensor sample_idx,
                 torch::Tensor chunks, torch::Tensor split_feat,
                 torch::Tensor split_bin, int64_t n,
                 torch::Tensor out_counts) {
-    auto stream = c10::hip::getCurrentHIPStream().stream();
-    hipError_t err = skdist_part_count(
+    const int64_t n_chunks =
+        check_part(codes, sample_idx, chunks, split_feat, split_bin, n);
+    check_vec(out_counts, torch::kInt32, n_chunks, "out_counts");
+    if (n_chunks == 0) return;
+    launched(skdist_part_count(
         codes.data_ptr(), sample_idx.data_ptr(), chunks.data_ptr(),
         split_feat.data_ptr(), split_bin.data_ptr(), n,
-        (int)codes.size(1), (int)chunks.size(0), out_counts.data_ptr(),
-        stream);
-    TORCH_CHECK(err == hipSuccess, "part_count: ", hipGetErrorString(err));
+        (int)codes.size(1), (int)n_chunks, out_counts.data_ptr(),
+        cur_stream()), "part_count");
 }
 
 void part_scatter(torch::Tensor codes, torch::Tensor sample_idx_in,
@@ -612,83 +614,54 @@ void part_scatter(torch::Tensor codes, torch::Tensor sample_idx_in,
                   torch::Tensor split_bin, torch::Tensor left_base,
                   torch::Tensor right_base, int64_t n,
                   torch::Tensor sample_idx_out) {
-    auto stream = c10::hip::getCurrentHIPStream().stream();
-    hipError_t err = skdist_part_scatter(
+    const int64_t n_chunks =
+        check_part(codes, sample_idx_in, chunks, split_feat, split_bin, n);
+    check_2d(sample_idx_out, torch::kInt32, sample_idx_in.size(0), n,
+             "sample_idx_out");
+    check_vec(left_base, torch::kInt32, n_chunks, "left_base");
+    check_vec(right_base, torch::kInt32, n_chunks, "right_base");
+    if (n_chunks == 0) return;
+    launched(skdist_part_scatter(
         codes.data_ptr(), sample_idx_in.data_ptr(), chunks.data_ptr(),
         split_feat.data_ptr(), split_bin.data_ptr(), left_base.data_ptr(),
-        right_base.data_ptr(), n, (int)codes.size(1),
-        (int)chunks.size(0), sample_idx_out.data_ptr(), stream);
-    TORCH_CHECK(err == hipSuccess, "part_scatter: ",
-                hipGetErrorString(err));
+        right_base.data_ptr(), n, (int)codes.size(1), (int)n_chunks,
+        sample_idx_out.data_ptr(), cur_stream()), "part_scatter");
+}
+
+// dense X [rows, f] f32; returns rows
+int64_t check_dense_x(const torch::Tensor& X) {
+    check_t(X, torch::kFloat32, "X");
+    TORCH_CHECK(X.dim() == 2 && X.size(1) >= 1 && X.size(1) < (1LL << 31),
+                "X must be [rows, f]");
+    return X.size(0);
 }
 
 void forest_predict(torch::Tensor X, torch::Tensor feat, torch::Tensor thr,
                     torch::Tensor left, torch::Tensor right,
                     torch::Tensor roots, torch::Tensor values,
                     torch::Tensor out) {
-    for (auto* t : {&X, &thr, &values, &out}) {
-        CHECK_DEV(*t);
-        CHECK_CONT(*t);
-    }
-    auto stream = c10::hip::getCurrentHIPStream().stream();
-    hipError_t err = skdist_forest_predict(
+    const int64_t rows = check_dense_x(X);
+    check_nodes(feat, thr, left, right, roots);
+    const int64_t vs = check_payload(values, out, rows);
+    if (rows == 0) return;
+    launched(skdist_forest_predict(
         X.data_ptr(), feat.data_ptr(), thr.data_ptr(), left.data_ptr(),
         right.data_ptr(), roots.data_ptr(), values.data_ptr(),
-        out.data_ptr(), X.size(0), (int)X.size(1), (int)roots.size(0),
-        (int)values.size(1), stream);
-    TORCH_CHECK(err == hipSuccess, "forest_predict: ",
-                hipGetErrorString(err));
+        out.data_ptr(), rows, (int)X.size(1), (int)roots.numel(), (int)vs,
+        cur_stream()), "forest_predict");
 }
 
 void forest_apply(torch::Tensor X, torch::Tensor feat, torch::Tensor thr,
                   torch::Tensor left, torch::Tensor right,
                   torch::Tensor roots, torch::Tensor out_leaf) {
-    auto stream = c10::hip::getCurrentHIPStream().stream();
-    hipError_t err = skdist_forest_apply(
+    const int64_t rows = check_dense_x(X);
+    check_nodes(feat, thr, left, right, roots);
+    check_2d(out_leaf, torch::kInt32, rows, roots.numel(), "out_leaf");
+    if (rows == 0) return;
+    launched(skdist_forest_apply(
         X.data_ptr(), feat.data_ptr(), thr.data_ptr(), left.data_ptr(),
-        right.data_ptr(), roots.data_ptr(), out_leaf.data_ptr(), X.size(0),
-        (int)X.size(1), (int)roots.size(0), stream);
-    TORCH_CHECK(err == hipSuccess, "forest_apply: ",
-                hipGetErrorString(err));
-}
-
-// CSR inputs shared by the sparse tree kernels: indptr int64 [rows+1],
-// indices int32 [nnz], data f32 [nnz], all contiguous on the GPU
-void check_csr(const torch::Tensor& indptr, const torch::Tensor& indices,
-               const torch::Tensor& data, int64_t rows) {
-    for (auto* t : {&indptr, &indices, &data}) {
-        CHECK_DEV(*t);
-        CHECK_CONT(*t);
-        TORCH_CHECK(t->dim() == 1, "CSR arrays must be 1-D");
-    }
-    TORCH_CHECK(indptr.scalar_type() == torch::kInt64,
-                "indptr must be int64");
-    TORCH_CHECK(indices.scalar_type() == torch::kInt32,
-                "indices must be int32");
-    TORCH_CHECK(data.scalar_type() == torch::kFloat32, "data must be f32");
-    TORCH_CHECK(rows >= 0 && indptr.numel() == rows + 1,
-                "indptr must hold rows+1 offsets");
-    TORCH_CHECK(indices.numel() == data.numel(),
-                "indices and data differ in length");
-}
-
-// node arrays of a flattened forest: int32 / f32, equal lengths
-void check_nodes(const torch::Tensor& feat, const torch::Tensor& thr,
-                 const torch::Tensor& left, const torch::Tensor& right,
-                 const torch::Tensor& roots) {
-    for (auto* t : {&feat, &thr, &left, &right, &roots}) {
-        CHECK_DEV(*t);
-        CHECK_CONT(*t);
-    }
-    for (auto* t : {&feat, &left, &right, &roots})
-        TORCH_CHECK(t->scalar_type() == torch::kInt32,
-                    "feat/left/right/roots must be int32");
-    TORCH_CHECK(thr.scalar_type() == torch::kFloat32, "thr must be f32");
-    TORCH_CHECK(thr.numel() == feat.numel() &&
-                    left.numel() == feat.numel() &&
-                    right.numel() == feat.numel(),
-                "node arrays differ in length");
-    TORCH_CHECK(roots.numel() >= 1 && feat.numel() >= 1, "empty forest");
+        right.data_ptr(), roots.data_ptr(), out_leaf.data_ptr(), rows,
+        (int)X.size(1), (int)roots.numel(), cur_stream()), "forest_apply");
 }
 
 void forest_predict_csr(torch::Tensor indptr, torch::Tensor indices,
@@ -696,28 +669,17 @@ void forest_predict_csr(torch::Tensor indptr, torch::Tensor indices,
                         torch::Tensor thr, torch::Tensor left,
                         torch::Tensor right, torch::Tensor roots,
                         torch::Tensor values, torch::Tensor out) {
-    const int64_t rows = out.dim() == 2 ? out.size(0) : -1;
+    const int64_t rows = rows_of(out);
     check_csr(indptr, indices, data, rows);
     check_nodes(feat, thr, left, right, roots);
-    for (auto* t : {&values, &out}) {
-        CHECK_DEV(*t);
-        CHECK_CONT(*t);
-        TORCH_CHECK(t->scalar_type() == torch::kFloat32 && t->dim() == 2,
-                    "values/out must be 2-D f32");
-    }
-    const int64_t vs = values.size(1);
-    TORCH_CHECK(vs >= 1 && vs <= 32,
-                "forest_predict_csr carries <= 32 payload values (MAXVS)");
-    TORCH_CHECK(out.size(1) == vs, "out must be [rows, vs]");
-    auto stream = c10::hip::getCurrentHIPStream().stream();
-    hipError_t err = skdist_forest_predict_csr(
+    const int64_t vs = check_payload(values, out, rows);
+    if (rows == 0) return;
+    launched(skdist_forest_predict_csr(
         indptr.data_ptr(), indices.data_ptr(), data.data_ptr(),
         feat.data_ptr(), thr.data_ptr(), left.data_ptr(),
         right.data_ptr(), roots.data_ptr(), values.data_ptr(),
         out.data_ptr(), rows, indices.numel(), (int)roots.numel(),
-        (int)vs, stream);
-    TORCH_CHECK(err == hipSuccess, "forest_predict_csr: ",
-                hipGetErrorString(err));
+        (int)vs, cur_stream()), "forest_predict_csr");
 }
 
 void forest_apply_csr(torch::Tensor indptr, torch::Tensor indices,
@@ -725,50 +687,37 @@ void forest_apply_csr(torch::Tensor indptr, torch::Tensor indices,
                       torch::Tensor thr, torch::Tensor left,
                       torch::Tensor right, torch::Tensor roots,
                       torch::Tensor out_leaf) {
-    const int64_t rows = out_leaf.dim() == 2 ? out_leaf.size(0) : -1;
+    const int64_t rows = rows_of(out_leaf);
     check_csr(indptr, indices, data, rows);
     check_nodes(feat, thr, left, right, roots);
-    CHECK_DEV(out_leaf);
-    CHECK_CONT(out_leaf);
-    TORCH_CHECK(out_leaf.scalar_type() == torch::kInt32,
-                "out_leaf must be int32");
-    TORCH_CHECK(out_leaf.size(1) == roots.numel(),
-                "out_leaf must be [rows, n_trees]");
-    auto stream = c10::hip::getCurrentHIPStream().stream();
-    hipError_t err = skdist_forest_apply_csr(
+    check_2d(out_leaf, torch::kInt32, rows, roots.numel(), "out_leaf");
+    if (rows == 0) return;
+    launched(skdist_forest_apply_csr(
         indptr.data_ptr(), indices.data_ptr(), data.data_ptr(),
         feat.data_ptr(), thr.data_ptr(), left.data_ptr(),
         right.data_ptr(), roots.data_ptr(), out_leaf.data_ptr(), rows,
-        indices.numel(), (int)roots.numel(), stream);
-    TORCH_CHECK(err == hipSuccess, "forest_apply_csr: ",
-                hipGetErrorString(err));
+        indices.numel(), (int)roots.numel(), cur_stream()),
+        "forest_apply_csr");
 }
 
 void bin_csr(torch::Tensor indptr, torch::Tensor indices,
              torch::Tensor data, torch::Tensor edges, torch::Tensor zc,
              torch::Tensor codes, int64_t f) {
-    TORCH_CHECK(codes.dim() == 2, "codes must be [n, fp]");
-    const int64_t n = codes.size(0), fp = codes.size(1);
+    const int64_t n = rows_of(codes);
     check_csr(indptr, indices, data, n);
-    for (auto* t : {&edges, &zc, &codes}) {
-        CHECK_DEV(*t);
-        CHECK_CONT(*t);
-    }
-    TORCH_CHECK(codes.scalar_type() == torch::kUInt8, "codes must be u8");
-    TORCH_CHECK(zc.scalar_type() == torch::kUInt8 && zc.numel() == fp,
-                "zc must be u8 [fp]");
-    TORCH_CHECK(fp % 4 == 0 && f >= 1 && f <= fp && fp < (1LL << 31),
-                "fp must be f padded to a multiple of 4");
-    TORCH_CHECK(edges.scalar_type() == torch::kFloat32 &&
-                    edges.dim() == 2 && edges.size(0) == f &&
+    const int64_t fp = check_codes(codes, n);
+    check_vec(zc, torch::kUInt8, fp, "zc");
+    TORCH_CHECK(f >= 1 && f <= fp, "fp must be f padded to a multiple of 4");
+    check_t(edges, torch::kFloat32, "edges");
+    TORCH_CHECK(edges.dim() == 2 && edges.size(0) == f &&
                     edges.size(1) <= 255,
                 "edges must be f32 [f, nbins-1] with nbins <= 256");
-    auto stream = c10::hip::getCurrentHIPStream().stream();
-    hipError_t err = skdist_bin_csr(
+    if (n == 0) return;
+    launched(skdist_bin_csr(
         indptr.data_ptr(), indices.data_ptr(), data.data_ptr(),
         edges.data_ptr(), zc.data_ptr(), codes.data_ptr(), n,
-        indices.numel(), (int)f, (int)fp, (int)edges.size(1), stream);
-    TORCH_CHECK(err == hipSuccess, "bin_csr: ", hipGetErrorString(err));
+        indices.numel(), (int)f, (int)fp, (int)edges.size(1), cur_stream()),
+        "bin_csr");
 }
 
 void score_fold(torch::Tensor Xf, torch::Tensor WbfT, torch::Tensor yf,
@@ -887,12 +836,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "tokenize + murmur3 feature hashing -> COO pairs");
     m.def("hash_vectorize_utf8", &hash_vectorize_utf8,
           "UTF-8 tokenize + murmur3 feature hashing -> COO pairs");
-    m.def("tree_hist", &tree_hist, "per-(node,feature,bin) stats");
-    m.def("tree_split", &tree_split, "best split per frontier node");
-    m.def("tree_hist_w", &tree_hist_w,
-          "per-(node,feature,bin) (W,Wy,Wyy,C) stats with f32 row weights");
-    m.def("tree_split_w", &tree_split_w,
-          "best split per frontier node, min-leaf on a count stat");
+    m.def("tree_hist", &tree_hist,
+          "per-(node,feature,bin) stats: class counts, (w,wy,wyy), or "
+          "(W,Wy,Wyy,C) with f32 row weights");
+    m.def("tree_split", &tree_split,
+          "best split per frontier node; min-leaf on the weight sums "
+          "(cnt_stat = -1) or on a count stat");
     m.def("part_count", &part_count, "partition phase A: left counts");
     m.def("part_scatter", &part_scatter, "partition phase B: scatter");
     m.def("forest_predict", &forest_predict, "batched forest inference");

@@ -6,6 +6,12 @@
 // table resident in HBM (small enough to sit in L2/L3), and every thread
 // walks all trees for one row, accumulating leaf payloads in registers.
 //
+// There is ONE walk (descend) and ONE predict / apply body, templated on a
+// row accessor with a single `float at(int jf)`; the four kernels are
+// predict/apply x dense/CSR instantiations of them.  One thread per row and
+// trees in order t = 0..T-1, so the accumulation order — and therefore
+// every output bit — is the same for a CSR row and for its dense copy.
+//
 // Layouts:
 //   X       [rows][f]  f32 row-major
 //   feat    [total_nodes] int32   (-1 = leaf; leaf's `left` indexes values)
@@ -13,100 +19,23 @@
 //   left/right [total_nodes] int32 (absolute node ids, pre-offset per tree)
 //   roots   [n_trees] int32
 //   values  [n_values][vs] f32
-#include "common.h"
-
-#define MAXVS 32
-
-extern "C" __global__ __launch_bounds__(256) void k_forest_predict(
-    const float* __restrict__ X, const int* __restrict__ feat,
-    const float* __restrict__ thr, const int* __restrict__ left,
-    const int* __restrict__ right, const int* __restrict__ roots,
-    const float* __restrict__ values, float* __restrict__ out,
-    long long rows, int f, int n_trees, int vs) {
-    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= rows) return;
-    const float* x = X + r * f;
-    float acc[MAXVS];
-#pragma unroll
-    for (int c = 0; c < MAXVS; ++c) acc[c] = 0.f;
-    for (int t = 0; t < n_trees; ++t) {
-        int node = roots[t];
-        int jf = feat[node];
-        while (jf >= 0) {
-            node = (x[jf] <= thr[node]) ? left[node] : right[node];
-            jf = feat[node];
-        }
-        const float* v = values + (long long)left[node] * vs;
-#pragma unroll
-        for (int c = 0; c < MAXVS; ++c)
-            if (c < vs) acc[c] += v[c];
-    }
-    const float inv = 1.f / (float)n_trees;
-#pragma unroll
-    for (int c = 0; c < MAXVS; ++c)
-        if (c < vs) out[r * vs + c] = acc[c] * inv;
-}
-
-extern "C" __global__ __launch_bounds__(256) void k_forest_apply(
-    const float* __restrict__ X, const int* __restrict__ feat,
-    const float* __restrict__ thr, const int* __restrict__ left,
-    const int* __restrict__ right, const int* __restrict__ roots,
-    int* __restrict__ out_leaf, long long rows, int f, int n_trees) {
-    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= rows) return;
-    const float* x = X + r * f;
-    for (int t = 0; t < n_trees; ++t) {
-        int node = roots[t];
-        int jf = feat[node];
-        while (jf >= 0) {
-            node = (x[jf] <= thr[node]) ? left[node] : right[node];
-            jf = feat[node];
-        }
-        out_leaf[r * n_trees + t] = node;
-    }
-}
-
-extern "C" hipError_t skdist_forest_predict(
-    const void* X, const void* feat, const void* thr, const void* left,
-    const void* right, const void* roots, const void* values, void* out,
-    long long rows, int f, int n_trees, int vs, hipStream_t stream) {
-    if (vs > MAXVS) return hipErrorInvalidValue;
-    const int blocks = (int)((rows + 255) / 256);
-    hipLaunchKernelGGL(k_forest_predict, dim3(blocks), dim3(256), 0,
-                       stream, (const float*)X, (const int*)feat,
-                       (const float*)thr, (const int*)left,
-                       (const int*)right, (const int*)roots,
-                       (const float*)values, (float*)out, rows, f, n_trees,
-                       vs);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t skdist_forest_apply(
-    const void* X, const void* feat, const void* thr, const void* left,
-    const void* right, const void* roots, void* out_leaf, long long rows,
-    int f, int n_trees, hipStream_t stream) {
-    const int blocks = (int)((rows + 255) / 256);
-    hipLaunchKernelGGL(k_forest_apply, dim3(blocks), dim3(256), 0, stream,
-                       (const float*)X, (const int*)feat,
-                       (const float*)thr, (const int*)left,
-                       (const int*)right, (const int*)roots,
-                       (int*)out_leaf, rows, f, n_trees);
-    return hipGetLastError();
-}
-
-// ---------------------------------------------------------------------- //
-// CSR rows (scipy-sparse X, never densified)
 //
+// CSR rows (scipy-sparse X, never densified):
 //   indptr  [rows+1] int64   (rebased so indptr[0] == 0 for the chunk)
 //   indices [nnz]    int32   ascending within each row, no duplicates
 //   data    [nnz]    f32
-//
-// Same walk as the dense kernels with x[jf] replaced by a binary search of
-// the row's index range: the stored value when column jf is present, 0.0f
-// otherwise.  One thread per row and trees in order t = 0..T-1, so the
-// accumulation order — and therefore every output bit — equals the dense
-// kernel on X.toarray().  Any nnz per row from 0 to f takes this one path.
-// ---------------------------------------------------------------------- //
+#include "common.h"
+#include "tree_api.h"
+
+#define MAXVS 32
+
+struct DenseRow {
+    const float* __restrict__ x;
+    __device__ __forceinline__ DenseRow(const float* X, long long r, int f)
+        : x(X + r * f) {}
+    __device__ __forceinline__ float at(int jf) const { return x[jf]; }
+};
+
 static __device__ __forceinline__ float csr_lookup(
     const int* __restrict__ indices, const float* __restrict__ data,
     long long lo, long long hi, int jf) {
@@ -120,29 +49,54 @@ static __device__ __forceinline__ float csr_lookup(
     return 0.f;
 }
 
-extern "C" __global__ __launch_bounds__(256) void k_forest_predict_csr(
-    const long long* __restrict__ indptr, const int* __restrict__ indices,
-    const float* __restrict__ data, const int* __restrict__ feat,
+// x[jf] is a binary search of the row's index range [lo, hi): the stored
+// value when column jf is present, 0.0f otherwise.  Any nnz per row from 0
+// to f takes this one path.
+struct CsrRow {
+    const int* __restrict__ indices;
+    const float* __restrict__ data;
+    long long lo, hi;
+    __device__ __forceinline__ CsrRow(const long long* indptr,
+                                      const int* indices_,
+                                      const float* data_, long long r,
+                                      long long nnz)
+        : indices(indices_), data(data_), lo(indptr[r]), hi(indptr[r + 1]) {
+        if (lo < 0) lo = 0;
+        if (hi > nnz) hi = nnz;
+    }
+    __device__ __forceinline__ float at(int jf) const {
+        return csr_lookup(indices, data, lo, hi, jf);
+    }
+};
+
+// root-to-leaf descent of tree t; returns the leaf's node id
+template <typename Row>
+static __device__ __forceinline__ int descend(
+    const Row& row, const int* __restrict__ feat,
+    const float* __restrict__ thr, const int* __restrict__ left,
+    const int* __restrict__ right, const int* __restrict__ roots, int t) {
+    int node = roots[t];
+    int jf = feat[node];
+    while (jf >= 0) {
+        node = (row.at(jf) <= thr[node]) ? left[node] : right[node];
+        jf = feat[node];
+    }
+    return node;
+}
+
+// mean leaf payload over the trees -> out[r][0..vs)
+template <typename Row>
+static __device__ __forceinline__ void predict_row(
+    const Row& row, const int* __restrict__ feat,
     const float* __restrict__ thr, const int* __restrict__ left,
     const int* __restrict__ right, const int* __restrict__ roots,
-    const float* __restrict__ values, float* __restrict__ out,
-    long long rows, long long nnz, int n_trees, int vs) {
-    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= rows) return;
-    long long lo = indptr[r], hi = indptr[r + 1];
-    if (lo < 0) lo = 0;
-    if (hi > nnz) hi = nnz;
+    const float* __restrict__ values, float* __restrict__ out, long long r,
+    int n_trees, int vs) {
     float acc[MAXVS];
 #pragma unroll
     for (int c = 0; c < MAXVS; ++c) acc[c] = 0.f;
     for (int t = 0; t < n_trees; ++t) {
-        int node = roots[t];
-        int jf = feat[node];
-        while (jf >= 0) {
-            const float x = csr_lookup(indices, data, lo, hi, jf);
-            node = (x <= thr[node]) ? left[node] : right[node];
-            jf = feat[node];
-        }
+        const int node = descend(row, feat, thr, left, right, roots, t);
         const float* v = values + (long long)left[node] * vs;
 #pragma unroll
         for (int c = 0; c < MAXVS; ++c)
@@ -154,6 +108,54 @@ extern "C" __global__ __launch_bounds__(256) void k_forest_predict_csr(
         if (c < vs) out[r * vs + c] = acc[c] * inv;
 }
 
+// leaf node id per tree -> out_leaf[r][0..n_trees)
+template <typename Row>
+static __device__ __forceinline__ void apply_row(
+    const Row& row, const int* __restrict__ feat,
+    const float* __restrict__ thr, const int* __restrict__ left,
+    const int* __restrict__ right, const int* __restrict__ roots,
+    int* __restrict__ out_leaf, long long r, int n_trees) {
+    for (int t = 0; t < n_trees; ++t)
+        out_leaf[r * n_trees + t] =
+            descend(row, feat, thr, left, right, roots, t);
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_forest_predict(
+    const float* __restrict__ X, const int* __restrict__ feat,
+    const float* __restrict__ thr, const int* __restrict__ left,
+    const int* __restrict__ right, const int* __restrict__ roots,
+    const float* __restrict__ values, float* __restrict__ out,
+    long long rows, int f, int n_trees, int vs) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    predict_row(DenseRow(X, r, f), feat, thr, left, right, roots, values,
+                out, r, n_trees, vs);
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_forest_apply(
+    const float* __restrict__ X, const int* __restrict__ feat,
+    const float* __restrict__ thr, const int* __restrict__ left,
+    const int* __restrict__ right, const int* __restrict__ roots,
+    int* __restrict__ out_leaf, long long rows, int f, int n_trees) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    apply_row(DenseRow(X, r, f), feat, thr, left, right, roots, out_leaf, r,
+              n_trees);
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_forest_predict_csr(
+    const long long* __restrict__ indptr, const int* __restrict__ indices,
+    const float* __restrict__ data, const int* __restrict__ feat,
+    const float* __restrict__ thr, const int* __restrict__ left,
+    const int* __restrict__ right, const int* __restrict__ roots,
+    const float* __restrict__ values, float* __restrict__ out,
+    long long rows, long long nnz, int n_trees, int vs) {
+    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= rows) return;
+    predict_row(CsrRow(indptr, indices, data, r, nnz), feat, thr, left,
+                right, roots, values, out, r, n_trees, vs);
+}
+
 extern "C" __global__ __launch_bounds__(256) void k_forest_apply_csr(
     const long long* __restrict__ indptr, const int* __restrict__ indices,
     const float* __restrict__ data, const int* __restrict__ feat,
@@ -163,19 +165,43 @@ extern "C" __global__ __launch_bounds__(256) void k_forest_apply_csr(
     int n_trees) {
     const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
     if (r >= rows) return;
-    long long lo = indptr[r], hi = indptr[r + 1];
-    if (lo < 0) lo = 0;
-    if (hi > nnz) hi = nnz;
-    for (int t = 0; t < n_trees; ++t) {
-        int node = roots[t];
-        int jf = feat[node];
-        while (jf >= 0) {
-            const float x = csr_lookup(indices, data, lo, hi, jf);
-            node = (x <= thr[node]) ? left[node] : right[node];
-            jf = feat[node];
-        }
-        out_leaf[r * n_trees + t] = node;
-    }
+    apply_row(CsrRow(indptr, indices, data, r, nnz), feat, thr, left, right,
+              roots, out_leaf, r, n_trees);
+}
+
+// ---------------------------------------------------------------------- //
+// C launchers: one thread per row, block 256
+// ---------------------------------------------------------------------- //
+static inline dim3 row_grid(long long rows) {
+    return dim3((unsigned)((rows + 255) / 256));
+}
+
+extern "C" hipError_t skdist_forest_predict(
+    const void* X, const void* feat, const void* thr, const void* left,
+    const void* right, const void* roots, const void* values, void* out,
+    long long rows, int f, int n_trees, int vs, hipStream_t stream) {
+    if (vs > MAXVS) return hipErrorInvalidValue;
+    if (rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_forest_predict, row_grid(rows), dim3(256), 0,
+                       stream, (const float*)X, (const int*)feat,
+                       (const float*)thr, (const int*)left,
+                       (const int*)right, (const int*)roots,
+                       (const float*)values, (float*)out, rows, f, n_trees,
+                       vs);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t skdist_forest_apply(
+    const void* X, const void* feat, const void* thr, const void* left,
+    const void* right, const void* roots, void* out_leaf, long long rows,
+    int f, int n_trees, hipStream_t stream) {
+    if (rows <= 0) return hipSuccess;
+    hipLaunchKernelGGL(k_forest_apply, row_grid(rows), dim3(256), 0, stream,
+                       (const float*)X, (const int*)feat,
+                       (const float*)thr, (const int*)left,
+                       (const int*)right, (const int*)roots,
+                       (int*)out_leaf, rows, f, n_trees);
+    return hipGetLastError();
 }
 
 extern "C" hipError_t skdist_forest_predict_csr(
@@ -185,8 +211,7 @@ extern "C" hipError_t skdist_forest_predict_csr(
     long long nnz, int n_trees, int vs, hipStream_t stream) {
     if (vs > MAXVS) return hipErrorInvalidValue;
     if (rows <= 0) return hipSuccess;
-    const int blocks = (int)((rows + 255) / 256);
-    hipLaunchKernelGGL(k_forest_predict_csr, dim3(blocks), dim3(256), 0,
+    hipLaunchKernelGGL(k_forest_predict_csr, row_grid(rows), dim3(256), 0,
                        stream, (const long long*)indptr,
                        (const int*)indices, (const float*)data,
                        (const int*)feat, (const float*)thr,
@@ -202,8 +227,7 @@ extern "C" hipError_t skdist_forest_apply_csr(
     const void* roots, void* out_leaf, long long rows, long long nnz,
     int n_trees, hipStream_t stream) {
     if (rows <= 0) return hipSuccess;
-    const int blocks = (int)((rows + 255) / 256);
-    hipLaunchKernelGGL(k_forest_apply_csr, dim3(blocks), dim3(256), 0,
+    hipLaunchKernelGGL(k_forest_apply_csr, row_grid(rows), dim3(256), 0,
                        stream, (const long long*)indptr,
                        (const int*)indices, (const float*)data,
                        (const int*)feat, (const float*)thr,

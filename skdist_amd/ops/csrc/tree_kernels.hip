@@ -5,6 +5,7 @@
 // skdist/distribute/ensemble.py:68-109).  A batch of TB trees grows
 // level-synchronously against ONE HBM-resident binned copy of X:
 //
+//   K0 k_bin_csr:      CSR -> uint8 codes (scipy-sparse X)
 //   K1 k_tree_hist:    per-(node,feature,bin) weighted stats, LDS-staged
 //      k_tree_hist_w:  the regression stats with a real-valued f32 row-weight
 //                      plane on top of the uint8 one, plus a row-count slot
@@ -15,6 +16,11 @@
 //   K3 k_part_count:   per-chunk left-row counts for the stable partition
 //   K4 k_part_scatter: stable partition of each node's sample segment
 //
+// K1 and K2 have ONE body each (tree_hist_body<ROW_W>,
+// tree_split_body<COUNTED>) behind the paired kernel names, and ONE checked
+// launcher each (tree_api.h) that picks the instantiation: skdist_tree_hist
+// by row_w != nullptr, skdist_tree_split by cnt_stat >= 0.
+//
 // Host orchestration + torch eager reference: skdist_amd/models/forest.py.
 //
 // Layouts:
@@ -23,7 +29,7 @@
 //   sample_idx [TB][n]   int32   per-tree row ids, node segments contiguous
 //   weights    [TB][n]   uint8   bootstrap multiplicities (0 = out of bag)
 //   row_w      [n]       f32     real-valued row weights, shared by all trees
-//                                     of the batch (k_tree_hist_w only)
+//                                     of the batch (ROW_W instantiation only)
 //   hist       [NF][f][nbins][S] f32   S = n_classes (cls) | 3 (w,wy,wyy)
 //                                       | 4 (W,Wy,Wyy,C) with row_w, where
 //                                       w = weights*row_w and C = Σ weights
@@ -38,6 +44,7 @@
 // count slot C is integer-valued like the class counts, so it is exact and
 // the min_samples_* tests that read it do not depend on arrival order.
 #include "common.h"
+#include "tree_api.h"
 
 #define WAVE 64
 
@@ -57,14 +64,38 @@ static __device__ __forceinline__ unsigned wang_hash(unsigned s) {
 // ---------------------------------------------------------------------- //
 typedef __attribute__((ext_vector_type(4))) unsigned char uchar4v;
 
-extern "C" __global__ __launch_bounds__(256) void k_tree_hist(
-    const unsigned char* __restrict__ codes,    // [n][fp] row-major
-    const int* __restrict__ y_int,              // [n] (cls) or nullptr
-    const float* __restrict__ y_f,              // [n] (reg) or nullptr
-    const unsigned char* __restrict__ weights,  // [TB][n]
-    const int* __restrict__ sample_idx,         // [TB][n]
-    const int* __restrict__ chunks,             // [n_chunks][4]
-    float* __restrict__ hist,                   // [NF][f][nbins][S]
+// one row's contribution to one (feature, bin) cell — cls: one atomic on
+// the row's class slot; reg: (w, wy, wyy); reg + row_w: the count m as well
+template <bool ROW_W>
+static __device__ __forceinline__ void hist_cell_add(
+    float* h, int is_cls, int stat, float w, float v1, float v2, float m) {
+    if (is_cls) {
+        atomicAdd(h + stat, w);
+    } else {
+        atomicAdd(h + 0, w);
+        atomicAdd(h + 1, v1);
+        atomicAdd(h + 2, v2);
+        if (ROW_W) atomicAdd(h + 3, m);
+    }
+}
+
+// ROW_W: a real-valued f32 row-weight plane on top of the uint8 one
+// (regression / gradient stats only, so is_cls is the constant false and
+// S the constant 4 there).  m = the tree's uint8 multiplicity; the cell
+// weight is w = m (no row_w) or m * row_w, and with row_w a fourth stat
+// keeps the row count C = Σ m.  The __restrict__ qualifiers stay on the
+// kernel wrappers' own parameters: repeated here they only add per-call
+// alias scopes on top of the same facts.
+template <bool ROW_W>
+static __device__ __forceinline__ void tree_hist_body(
+    const unsigned char* codes,    // [n][fp] row-major
+    const int* y_int,              // [n] (cls) or nullptr
+    const float* y_f,              // [n] (reg) or nullptr
+    const float* row_w,            // [n] (ROW_W) or nullptr
+    const unsigned char* weights,  // [TB][n]
+    const int* sample_idx,         // [TB][n]
+    const int* chunks,             // [n_chunks][4]
+    float* hist,                   // [NF][f][nbins][S]
     long long n, int f, int fp, int nbins, int S, int is_cls, int fg) {
     extern __shared__ float lds[];
     const int chunk = blockIdx.x;
@@ -86,7 +117,8 @@ extern "C" __global__ __launch_bounds__(256) void k_tree_hist(
     const bool vec = (g0 & 3) == 0;
     for (int r = threadIdx.x; r < row_count; r += blockDim.x) {
         const int i = si[r];
-        const float w = (float)wrow[i];
+        const float m = (float)wrow[i];
+        const float w = ROW_W ? m * row_w[i] : m;
         int stat = 0;
         float v1 = 0.f, v2 = 0.f;
         if (is_cls) {
@@ -105,27 +137,16 @@ extern "C" __global__ __launch_bounds__(256) void k_tree_hist(
                 for (int t = 0; t < 4; ++t) {
                     const int jj = q * 4 + t;
                     if (jj >= nf_g) break;
-                    float* h = lds + ((jj * nbins + (int)b4[t]) * S);
-                    if (is_cls) {
-                        atomicAdd(h + stat, w);
-                    } else {
-                        atomicAdd(h + 0, w);
-                        atomicAdd(h + 1, v1);
-                        atomicAdd(h + 2, v2);
-                    }
+                    hist_cell_add<ROW_W>(
+                        lds + ((jj * nbins + (int)b4[t]) * S), is_cls, stat,
+                        w, v1, v2, m);
                 }
             }
         } else {
-            for (int jj = 0; jj < nf_g; ++jj) {
-                float* h = lds + ((jj * nbins + (int)crow[jj]) * S);
-                if (is_cls) {
-                    atomicAdd(h + stat, w);
-                } else {
-                    atomicAdd(h + 0, w);
-                    atomicAdd(h + 1, v1);
-                    atomicAdd(h + 2, v2);
-                }
-            }
+            for (int jj = 0; jj < nf_g; ++jj)
+                hist_cell_add<ROW_W>(
+                    lds + ((jj * nbins + (int)crow[jj]) * S), is_cls, stat,
+                    w, v1, v2, m);
         }
     }
     __syncthreads();
@@ -137,78 +158,26 @@ extern "C" __global__ __launch_bounds__(256) void k_tree_hist(
     }
 }
 
-// ---------------------------------------------------------------------- //
-// K1w: histogram build with a real-valued row-weight plane (regression /
-// gradient stats only).  Same grid, chunk table and LDS staging as
-// k_tree_hist; four stats per cell: W = Σ m·row_w, Wy, Wyy and the row
-// count C = Σ m (m = the tree's uint8 multiplicity).
+extern "C" __global__ __launch_bounds__(256) void k_tree_hist(
+    const unsigned char* __restrict__ codes, const int* __restrict__ y_int,
+    const float* __restrict__ y_f, const unsigned char* __restrict__ weights,
+    const int* __restrict__ sample_idx, const int* __restrict__ chunks,
+    float* __restrict__ hist, long long n, int f, int fp, int nbins, int S,
+    int is_cls, int fg) {
+    tree_hist_body<false>(codes, y_int, y_f, nullptr, weights, sample_idx,
+                          chunks, hist, n, f, fp, nbins, S, is_cls, fg);
+}
+
 // dynamic LDS: fg * nbins * 4 floats
-// ---------------------------------------------------------------------- //
 extern "C" __global__ __launch_bounds__(256) void k_tree_hist_w(
-    const unsigned char* __restrict__ codes,    // [n][fp] row-major
-    const float* __restrict__ y_f,              // [n]
-    const float* __restrict__ row_w,            // [n]
-    const unsigned char* __restrict__ weights,  // [TB][n]
-    const int* __restrict__ sample_idx,         // [TB][n]
-    const int* __restrict__ chunks,             // [n_chunks][4]
-    float* __restrict__ hist,                   // [NF][f][nbins][4]
-    long long n, int f, int fp, int nbins, int fg) {
-    extern __shared__ float lds[];
-    const int chunk = blockIdx.x;
-    const int g0 = blockIdx.y * fg;
-    const int nf_g = min(fg, f - g0);
-    const int node_slot = chunks[chunk * 4 + 0];
-    const int tree_slot = chunks[chunk * 4 + 1];
-    const int row_start = chunks[chunk * 4 + 2];
-    const int row_count = chunks[chunk * 4 + 3];
-
-    const int lds_sz = nf_g * nbins * 4;
-    for (int i = threadIdx.x; i < lds_sz; i += blockDim.x) lds[i] = 0.f;
-    __syncthreads();
-
-    const int* si = sample_idx + (long long)tree_slot * n + row_start;
-    const unsigned char* wrow = weights + (long long)tree_slot * n;
-    const bool vec = (g0 & 3) == 0;
-    for (int r = threadIdx.x; r < row_count; r += blockDim.x) {
-        const int i = si[r];
-        const float m = (float)wrow[i];
-        const float w = m * row_w[i];
-        const float yv = y_f[i];
-        const float v1 = w * yv;
-        const float v2 = w * yv * yv;
-        const unsigned char* crow = codes + (long long)i * fp + g0;
-        if (vec) {
-            const uchar4v* c4 = (const uchar4v*)crow;
-            for (int q = 0; q * 4 < nf_g; ++q) {
-                const uchar4v b4 = c4[q];
-                #pragma unroll
-                for (int t = 0; t < 4; ++t) {
-                    const int jj = q * 4 + t;
-                    if (jj >= nf_g) break;
-                    float* h = lds + ((jj * nbins + (int)b4[t]) * 4);
-                    atomicAdd(h + 0, w);
-                    atomicAdd(h + 1, v1);
-                    atomicAdd(h + 2, v2);
-                    atomicAdd(h + 3, m);
-                }
-            }
-        } else {
-            for (int jj = 0; jj < nf_g; ++jj) {
-                float* h = lds + ((jj * nbins + (int)crow[jj]) * 4);
-                atomicAdd(h + 0, w);
-                atomicAdd(h + 1, v1);
-                atomicAdd(h + 2, v2);
-                atomicAdd(h + 3, m);
-            }
-        }
-    }
-    __syncthreads();
-
-    float* gh = hist + ((long long)node_slot * f + g0) * nbins * 4;
-    for (int i = threadIdx.x; i < lds_sz; i += blockDim.x) {
-        const float v = lds[i];
-        if (v != 0.f) atomicAdd(gh + i, v);
-    }
+    const unsigned char* __restrict__ codes, const float* __restrict__ y_f,
+    const float* __restrict__ row_w,
+    const unsigned char* __restrict__ weights,
+    const int* __restrict__ sample_idx, const int* __restrict__ chunks,
+    float* __restrict__ hist, long long n, int f, int fp, int nbins,
+    int fg) {
+    tree_hist_body<true>(codes, nullptr, y_f, row_w, weights, sample_idx,
+                         chunks, hist, n, f, fp, nbins, 4, 0, fg);
 }
 
 // ---------------------------------------------------------------------- //
@@ -564,81 +533,64 @@ extern "C" __global__ __launch_bounds__(256) void k_part_scatter(
 // ---------------------------------------------------------------------- //
 extern "C" hipError_t skdist_tree_hist(
     const void* codes, const void* y_int, const void* y_f,
-    const void* weights, const void* sample_idx, const void* chunks,
-    void* hist, long long n, int f, int fp, int nbins, int S, int is_cls,
-    int fg, int n_chunks, hipStream_t stream) {
-    const int n_groups = (f + fg - 1) / fg;
-    const size_t lds = (size_t)fg * nbins * S * sizeof(float);
-    hipLaunchKernelGGL(k_tree_hist, dim3(n_chunks, n_groups), dim3(256),
-                       lds, stream, (const unsigned char*)codes,
-                       (const int*)y_int, (const float*)y_f,
-                       (const unsigned char*)weights,
-                       (const int*)sample_idx, (const int*)chunks,
-                       (float*)hist, n, f, fp, nbins, S, is_cls, fg);
-    return hipGetLastError();
-}
-
-extern "C" hipError_t skdist_tree_hist_w(
-    const void* codes, const void* y_f, const void* row_w,
-    const void* weights, const void* sample_idx, const void* chunks,
-    void* hist, long long n, int f, int fp, int nbins, int fg,
-    int n_chunks, hipStream_t stream) {
+    const void* row_w, const void* weights, const void* sample_idx,
+    const void* chunks, void* hist, long long n, int f, int fp, int nbins,
+    int S, int fg, int n_chunks, hipStream_t stream) {
     if (n_chunks <= 0) return hipSuccess;
-    const size_t lds = (size_t)fg * nbins * 4 * sizeof(float);
+    const size_t lds = (size_t)fg * nbins * S * sizeof(float);
     if (fg <= 0 || f <= 0 || fp % 4 != 0 || f > fp || nbins <= 0 ||
-        nbins > 256 || lds > 64 * 1024)
+        nbins > 256 || S <= 0 || lds > 64 * 1024)
         return hipErrorInvalidValue;
-    const int n_groups = (f + fg - 1) / fg;
-    hipLaunchKernelGGL(k_tree_hist_w, dim3(n_chunks, n_groups), dim3(256),
-                       lds, stream, (const unsigned char*)codes,
-                       (const float*)y_f, (const float*)row_w,
-                       (const unsigned char*)weights,
-                       (const int*)sample_idx, (const int*)chunks,
-                       (float*)hist, n, f, fp, nbins, fg);
+    // exactly one target; row_w rides the regression stats only (S = 4)
+    if ((y_int != nullptr) == (y_f != nullptr) ||
+        (row_w != nullptr && (y_f == nullptr || S != 4)))
+        return hipErrorInvalidValue;
+    const dim3 grid(n_chunks, (f + fg - 1) / fg);
+    if (row_w != nullptr)
+        hipLaunchKernelGGL(k_tree_hist_w, grid, dim3(256), lds, stream,
+                           (const unsigned char*)codes, (const float*)y_f,
+                           (const float*)row_w,
+                           (const unsigned char*)weights,
+                           (const int*)sample_idx, (const int*)chunks,
+                           (float*)hist, n, f, fp, nbins, fg);
+    else
+        hipLaunchKernelGGL(k_tree_hist, grid, dim3(256), lds, stream,
+                           (const unsigned char*)codes, (const int*)y_int,
+                           (const float*)y_f,
+                           (const unsigned char*)weights,
+                           (const int*)sample_idx, (const int*)chunks,
+                           (float*)hist, n, f, fp, nbins, S,
+                           (int)(y_int != nullptr), fg);
     return hipGetLastError();
 }
 
 extern "C" hipError_t skdist_tree_split(
     const void* hist, const void* node_seed, int n_frontier, int f,
     int nbins, int S, int is_cls, int crit, int m_features, int extra_mode,
-    float min_leaf_w, void* out_feat, void* out_bin, void* out_wl,
-    void* out_gain, void* out_imp, void* out_stats, void* out_lstats,
-    hipStream_t stream) {
-    // per-node parallelism is one thread per feature: size the block to
-    // f so low-f datasets don't idle 3/4 of each workgroup
-    const int threads = f >= 192 ? 256 : (f >= 96 ? 128 : 64);
-    hipLaunchKernelGGL(k_tree_split, dim3(n_frontier), dim3(threads), 0,
-                       stream, (const float*)hist,
-                       (const unsigned*)node_seed, f, nbins, S, is_cls,
-                       crit, m_features, extra_mode, min_leaf_w,
-                       (int*)out_feat, (int*)out_bin, (float*)out_wl,
-                       (float*)out_gain, (float*)out_imp,
-                       (float*)out_stats, (float*)out_lstats);
-    return hipGetLastError();
-}
-
-// cnt_stat < 0 is today's weight-sum rule (k_tree_split itself)
-extern "C" hipError_t skdist_tree_split_w(
-    const void* hist, const void* node_seed, int n_frontier, int f,
-    int nbins, int S, int is_cls, int crit, int m_features, int extra_mode,
     float min_leaf, int cnt_stat, void* out_feat, void* out_bin,
     void* out_wl, void* out_gain, void* out_imp, void* out_stats,
     void* out_lstats, hipStream_t stream) {
-    if (cnt_stat < 0)
-        return skdist_tree_split(hist, node_seed, n_frontier, f, nbins, S,
-                                 is_cls, crit, m_features, extra_mode,
-                                 min_leaf, out_feat, out_bin, out_wl,
-                                 out_gain, out_imp, out_stats, out_lstats,
-                                 stream);
-    if (cnt_stat >= S || S > 32) return hipErrorInvalidValue;
+    if (n_frontier <= 0) return hipSuccess;
+    if (S <= 0 || S > 32 || cnt_stat >= S) return hipErrorInvalidValue;
+    // per-node parallelism is one thread per feature: size the block to
+    // f so low-f datasets don't idle 3/4 of each workgroup
     const int threads = f >= 192 ? 256 : (f >= 96 ? 128 : 64);
-    hipLaunchKernelGGL(k_tree_split_w, dim3(n_frontier), dim3(threads), 0,
-                       stream, (const float*)hist,
-                       (const unsigned*)node_seed, f, nbins, S, is_cls,
-                       crit, m_features, extra_mode, min_leaf,
-                       (int*)out_feat, (int*)out_bin, (float*)out_wl,
-                       (float*)out_gain, (float*)out_imp,
-                       (float*)out_stats, (float*)out_lstats, cnt_stat);
+    if (cnt_stat < 0)
+        hipLaunchKernelGGL(k_tree_split, dim3(n_frontier), dim3(threads), 0,
+                           stream, (const float*)hist,
+                           (const unsigned*)node_seed, f, nbins, S, is_cls,
+                           crit, m_features, extra_mode, min_leaf,
+                           (int*)out_feat, (int*)out_bin, (float*)out_wl,
+                           (float*)out_gain, (float*)out_imp,
+                           (float*)out_stats, (float*)out_lstats);
+    else
+        hipLaunchKernelGGL(k_tree_split_w, dim3(n_frontier), dim3(threads),
+                           0, stream, (const float*)hist,
+                           (const unsigned*)node_seed, f, nbins, S, is_cls,
+                           crit, m_features, extra_mode, min_leaf,
+                           (int*)out_feat, (int*)out_bin, (float*)out_wl,
+                           (float*)out_gain, (float*)out_imp,
+                           (float*)out_stats, (float*)out_lstats, cnt_stat);
     return hipGetLastError();
 }
 
@@ -658,6 +610,7 @@ extern "C" hipError_t skdist_part_scatter(
     const void* split_feat, const void* split_bin, const void* left_base,
     const void* right_base, long long n, int fp, int n_chunks,
     void* sample_idx_out, hipStream_t stream) {
+    if (n_chunks <= 0) return hipSuccess;
     hipLaunchKernelGGL(k_part_scatter, dim3(n_chunks), dim3(256), 0,
                        stream, (const unsigned char*)codes,
                        (const int*)sample_idx_in, (const int*)chunks,

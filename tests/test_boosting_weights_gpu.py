@@ -64,17 +64,26 @@ def _hist_ref(codes, y, row_w, mult, si, segments, f, n_slots):
     return ref
 
 
-def _run_hist_w(codes, y, row_w, mult, si, segments, f, n_slots, fg):
+def _run_hist(codes, y_int, y_f, row_w, mult, si, segments, f, n_slots, fg,
+              S):
+    """The one ``tree_hist`` entry; None = that tensor is absent."""
     ext = require_hip()
     dev = "cuda"
     n = len(codes)
-    hist = torch.zeros(n_slots, f, NBINS, 4, dtype=torch.float32,
+    hist = torch.zeros(n_slots, f, NBINS, S, dtype=torch.float32,
                        device=dev)
-    t = lambda a: torch.as_tensor(np.ascontiguousarray(a), device=dev)
-    ext.tree_hist_w(t(codes), t(y), t(row_w), t(mult), t(si),
-                    t(_chunks(segments)), hist, n, f, NBINS, fg)
+    t = lambda a: torch.as_tensor(
+        np.ascontiguousarray(np.empty(0, np.float32) if a is None else a),
+        device=dev)
+    ext.tree_hist(t(codes), t(y_int), t(y_f), t(row_w), t(mult), t(si),
+                  t(_chunks(segments)), hist, n, f, NBINS, fg)
     torch.cuda.synchronize()
     return hist.cpu().numpy()
+
+
+def _run_hist_w(codes, y, row_w, mult, si, segments, f, n_slots, fg):
+    return _run_hist(codes, None, y, row_w, mult, si, segments, f, n_slots,
+                     fg, 4)
 
 
 def _assert_bit_equal(got, ref):
@@ -112,6 +121,56 @@ def test_tree_hist_w_small_segments_bit_equal(f, fg):
     _assert_bit_equal(got, ref)
 
 
+# the unweighted instantiation of the same body, same segments and groups:
+# (w, wy, wyy) is _hist_ref with row_w = 1 minus its count slot, and class
+# counts are sums of the uint8 multiplicities, so both are exact in f32
+def _small_segments(f):
+    sizes = [1, 63, 64, 257, 1000]
+    codes, y, _, mult, si = _hist_inputs(sum(sizes), f, 1, seed=1)
+    starts = np.cumsum([0] + sizes[:-1])
+    segments = [(k, 0, int(starts[k]), sizes[k]) for k in range(5)]
+    return codes, y, mult, si, segments
+
+
+@pytest.mark.parametrize("f,fg", [(3, 3), (7, 3)])
+def test_tree_hist_regression_small_segments_bit_equal(f, fg):
+    codes, y, mult, si, segments = _small_segments(f)
+    got = _run_hist(codes, None, y, None, mult, si, segments, f, 5, fg, 3)
+    ones = np.ones(len(codes), dtype=np.float32)
+    ref = _hist_ref(codes, y, ones, mult, si, segments, f, 5)[..., :3]
+    assert ref[..., 0].sum() > 0 and np.abs(ref[..., 1]).sum() > 0
+    _assert_bit_equal(got, np.ascontiguousarray(ref))
+
+
+@pytest.mark.parametrize("f,fg", [(3, 3), (7, 3)])
+def test_tree_hist_classification_small_segments_bit_equal(f, fg):
+    n_cls = 3
+    codes, _, mult, si, segments = _small_segments(f)
+    y_cls = np.random.default_rng(7).integers(0, n_cls, len(codes)).astype(
+        np.int32)
+    got = _run_hist(codes, y_cls, None, None, mult, si, segments, f, 5, fg,
+                    n_cls)
+    ref = np.zeros((5, f, NBINS, n_cls), dtype=np.float64)
+    for slot, tree, start, count in segments:
+        rows = si[tree, start:start + count].astype(np.int64)
+        m = mult[tree, rows].astype(np.float64)
+        for j in range(f):
+            np.add.at(ref[slot, j], (codes[rows, j], y_cls[rows]), m)
+    assert (ref.sum(axis=(0, 1, 2)) > 0).all()      # every class occurs
+    assert ref.sum() == f * sum(
+        mult[0, si[0, s:s + c]].sum() for _, _, s, c in segments)
+    _assert_bit_equal(got, ref)
+
+
+def test_tree_hist_rejects_lds_overflow():
+    """fg * nbins * S * 4 = 24 * 256 * 3 * 4 bytes = 72 KiB > 64 KiB."""
+    n, f = 300, 24
+    codes, y, _, mult, si = _hist_inputs(n, f, 1, seed=2)
+    with pytest.raises(RuntimeError, match="LDS"):
+        _run_hist(codes, None, y, None, mult, si, [(0, 0, 0, n)], f, 1, 24,
+                  3)
+
+
 def test_tree_hist_w_rejects_bad_row_w():
     n, f = 300, 4
     codes, y, row_w, mult, si = _hist_inputs(n, f, 1, seed=2)
@@ -126,7 +185,7 @@ def test_tree_hist_w_rejects_bad_row_w():
 # ---------------------------------------------------------------------- #
 # split rule on counts
 # ---------------------------------------------------------------------- #
-def _split(hist_np, S, min_leaf, cnt_stat, counted_binding=True):
+def _split(hist_np, S, min_leaf, cnt_stat):
     ext = require_hip()
     dev = "cuda"
     NF, f, nbins, _ = hist_np.shape
@@ -138,10 +197,7 @@ def _split(hist_np, S, min_leaf, cnt_stat, counted_binding=True):
     out = (oi(), oi(), of(NF), of(NF), of(NF), of(NF, S), of(NF, S))
     CRIT_MSE = 2
     args = (hist, seed, f, nbins, S, 0, CRIT_MSE, f, 0, float(min_leaf))
-    if counted_binding:
-        ext.tree_split_w(*args, *out, cnt_stat)
-    else:
-        ext.tree_split(*args, *out)
+    ext.tree_split(*args, *out, cnt_stat)
     torch.cuda.synchronize()
     return [o.cpu().numpy() for o in out]
 
@@ -180,12 +236,48 @@ def test_tree_split_w_min_leaf_counts_rows():
     # today's rule on the 3-slot copy: the weight sums are compared
     H3 = np.ascontiguousarray(H[..., :3])
     new = _split(H3, 3, 3, cnt_stat=-1)
-    old = _split(H3, 3, 3, cnt_stat=None, counted_binding=False)
-    for a, b in zip(new, old):
-        np.testing.assert_array_equal(a, b)
+    # all seven outputs against fp64 from H3 itself: the sums are exact,
+    # and the f32 quotients of these small integers round as fp64 does
+    for name, got, ref in zip(
+            ("feat", "bin", "wl", "gain", "imp", "stats", "lstats"), new,
+            _weight_sum_rule_ref(H3, 3)):
+        print(name, got.tolist(), ref.tolist())
+        np.testing.assert_array_equal(got, ref.astype(got.dtype), name)
     feat3, bin3 = new[0], new[1]
     assert feat3[0] == -1               # A: wl = 1.25 < 3
     assert (feat3[1], bin3[1]) == (0, 0)  # B: wl = 4 >= 3, higher gain
+
+
+def _weight_sum_rule_ref(H3, min_leaf):
+    """fp64 reference of the seven ``tree_split`` outputs on a one-feature
+    (W, Wy, Wyy) histogram [NF, 1, nbins, 3]: variance impurity, min-leaf
+    on the weight sums, first best bin.  A node without a valid cut reports
+    feat = bin = -1, wl = 0, gain = -1 and zero left stats."""
+    def var(s):
+        return max(s[2] / s[0] - (s[1] / s[0]) ** 2, 0.0) if s[0] > 0 else 0.0
+
+    NF, _, nbins, S = H3.shape
+    feat = np.full(NF, -1, dtype=np.int64)
+    bin_ = np.full(NF, -1, dtype=np.int64)
+    wl, gain, imp = np.zeros(NF), np.full(NF, -1.0), np.zeros(NF)
+    stats = H3[:, 0].sum(axis=1)
+    lstats = np.zeros((NF, S))
+    for k in range(NF):
+        p = stats[k]
+        imp[k] = var(p)
+        for b in range(nbins - 1):
+            l = H3[k, 0, :b + 1].sum(axis=0)
+            r = p - l
+            if l[0] < min_leaf or r[0] < min_leaf:
+                continue
+            g = imp[k] - (l[0] * var(l) + r[0] * var(r)) / p[0]
+            if g > gain[k] + 1e-12:
+                gain[k], bin_[k], wl[k], lstats[k] = g, b, l[0], l
+        if gain[k] > 0:
+            feat[k] = 0
+        else:
+            lstats[k] = 0.0
+    return feat, bin_, wl, gain, imp, stats, lstats
 
 
 # ---------------------------------------------------------------------- #

@@ -129,6 +129,59 @@ def test_flat_forest_matches_host():
     np.testing.assert_array_equal(ff.apply(X), host_apply)
 
 
+def test_flat_forest_matches_host_tree_walk():
+    """The dense kernels against the numpy HistTree walk, tree by tree
+    (257 rows: two blocks, the second with one row; 65 trees; vs = 2).
+
+    predict sums 65 payloads in [0, 1] in f32: each add rounds by at most
+    half an ulp of 64 (2^-18) and the mean divides the total by 65, so the
+    worst case is 2^-18 = 3.8e-6 from the fp64 mean; atol = 1e-5."""
+    X, y = _cls_data(257, 8, seed=11)
+    ds = BinnedDataset(X, y, "cuda", is_cls=True)
+    trees = ForestBuilder(ds, "gini", max_depth=5, bootstrap=True,
+                          tree_batch=65, engine="hip").build(list(range(65)))
+    assert len(trees) == 65 and trees[0].value.shape[1] == 2
+    assert len({len(t.feature) for t in trees}) > 1     # trees differ
+    ff = FlatForest(trees, "cuda")
+    host = np.mean([t.predict_proba(X).astype(np.float64) for t in trees],
+                   axis=0)
+    np.testing.assert_allclose(ff.predict_value(X), host, rtol=0, atol=1e-5)
+    np.testing.assert_array_equal(
+        ff.apply(X), np.column_stack([t.apply(X) for t in trees]))
+
+
+def _one_split_node_arrays():
+    t = lambda a, dt: torch.as_tensor(a, dtype=dt, device="cuda")
+    return (t([0, -1, -1], torch.int32), t([0.0, 0.0, 0.0], torch.float32),
+            t([1, 0, 1], torch.int32), t([2, 0, 0], torch.int32),
+            t([0], torch.int32))
+
+
+def test_forest_apply_rejects_wrong_out_width():
+    from skdist_amd.ops import require_hip
+
+    X = torch.zeros(5, 2, device="cuda")
+    out = torch.empty(5, 2, dtype=torch.int32, device="cuda")   # 1 tree
+    with pytest.raises(RuntimeError, match="out_leaf"):
+        require_hip().forest_apply(X, *_one_split_node_arrays(), out)
+
+
+def test_part_count_rejects_int64_split_feat():
+    from skdist_amd.ops import require_hip
+
+    n = 8
+    dev = "cuda"
+    codes = torch.zeros(n, 4, dtype=torch.uint8, device=dev)
+    si = torch.arange(n, dtype=torch.int32, device=dev).view(1, n)
+    chunks = torch.tensor([[0, 0, 0, n]], dtype=torch.int32, device=dev)
+    split_bin = torch.zeros(1, dtype=torch.int32, device=dev)
+    counts = torch.empty(1, dtype=torch.int32, device=dev)
+    with pytest.raises(RuntimeError, match="split_feat"):
+        require_hip().part_count(
+            codes, si, chunks, torch.zeros(1, dtype=torch.int64, device=dev),
+            split_bin, n, counts)
+
+
 def test_dist_predictor_uses_device_forest():
     X, y = _cls_data(2000, 8, seed=6)
     clf = DistRandomForestClassifier(

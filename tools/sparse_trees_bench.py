@@ -111,7 +111,7 @@ def _report(name, path, ts):
 
 def main():
     cases = args.cases.split(",")
-    csr_native = hasattr(F.FlatForest, "_predict_value_csr")
+    csr_native = hasattr(F, "_csr_row_chunks")
     print(f"package: {os.path.dirname(skdist_amd.__file__)}")
     print(f"device: {torch.cuda.get_device_name(0)}  rows: {args.rows}  "
           f"csr-native trees: {csr_native}", flush=True)

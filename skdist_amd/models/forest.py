@@ -92,11 +92,13 @@ class HistTree:
 
     ``feature[i] == -1`` marks a leaf; its ``left[i]`` indexes ``value``
     (leaf payload: class distribution [k] or mean [1]).  Internal nodes
-    send ``x[feature] <= threshold`` left.
+    send ``x[feature] <= threshold`` left.  ``missing_left`` (uint8
+    ``[node_count]`` or None) marks the nodes that send a NaN left as well;
+    without it a NaN goes right everywhere (``NaN <= t`` is false).
     """
 
     def __init__(self, feature, threshold, left, right, value, classes,
-                 n_features, importances):
+                 n_features, importances, missing_left=None):
         self.feature = feature
         self.threshold = threshold
         self.left = left
@@ -105,6 +107,7 @@ class HistTree:
         self.classes_ = classes
         self.n_features_in_ = n_features
         self.feature_importances_ = importances
+        self.missing_left = missing_left
 
     @property
     def node_count(self):
@@ -133,6 +136,10 @@ class HistTree:
             else:
                 xv = X[idx, f]
             go_left = xv <= self.threshold[nd]
+            # getattr: trees pickled before missing_left existed
+            ml = getattr(self, "missing_left", None)
+            if ml is not None:
+                go_left |= np.isnan(xv) & (ml[nd] != 0)
             node[idx] = np.where(go_left, self.left[nd], self.right[nd])
             active[idx] = self.feature[node[idx]] >= 0
         return node
@@ -294,13 +301,23 @@ class BinnedDataset:
     weight plane ``row_w`` next to the codes.  The builder then keeps four
     statistics per histogram cell, (W, Wy, Wyy, C): weight sums drive
     impurity, gain and leaf values while the row count C keeps
-    ``min_samples_*`` counts.  Without it nothing changes."""
+    ``min_samples_*`` counts.  Without it nothing changes.
+
+    ``allow_missing`` lets a dense X hold NaN (never ±inf).  If it holds
+    any, the top code ``missing_bin = nbins - 1`` is reserved for them and
+    the real values share ``nbins - 1`` bins whose last edge is ``+inf``;
+    if it holds none, edges and codes are the ones of ``allow_missing=
+    False`` and ``missing_bin`` is None.  A sparse X with a stored NaN
+    still raises."""
 
     def __init__(self, X, y, device, is_cls, classes=None, nbins=256,
-                 max_bin_sample=200_000, seed=0, row_weight=None):
+                 max_bin_sample=200_000, seed=0, row_weight=None,
+                 allow_missing=False):
         import scipy.sparse as sp
 
         self.device = torch.device(device)
+        self.allow_missing = bool(allow_missing)
+        self.missing_bin = None
         if sp.issparse(X):
             self._init_codes_csr(X, nbins, max_bin_sample, seed)
         else:
@@ -343,6 +360,11 @@ class BinnedDataset:
                 f"would take {gb:.1f} GB (> {limit:.0f} GB; set "
                 "SKDIST_AMD_DENSIFY_GB to raise the limit)")
         C = canonical_csr(X)
+        if self.allow_missing and np.isnan(C.data).any():
+            raise ValueError(
+                "Input X contains NaN: a sparse (CSR) X with a stored NaN "
+                "cannot be fitted, missing values are binned for dense X "
+                "only (pass a dense array, or impute the stored NaN)")
         check_finite(torch.from_numpy(C.data), "X")
         dev = self.device
 
@@ -386,7 +408,16 @@ class BinnedDataset:
         Xt = torch.as_tensor(X, device=self.device)
         from ._sgd import check_finite
 
-        check_finite(Xt, "X")
+        nan = None
+        if self.allow_missing:
+            nan = torch.isnan(Xt)
+            if not bool(nan.any()):
+                nan = None
+        if nan is None:
+            check_finite(Xt, "X")
+        elif bool(torch.isinf(Xt).any()):
+            raise ValueError(
+                "Input X contains infinity; missing values are NaN only")
 
         # per-feature quantile edges from a (seeded) row subsample
         if self.n > max_bin_sample:
@@ -396,9 +427,27 @@ class BinnedDataset:
             Xs = Xt[sub.to(self.device)]
         else:
             Xs = Xt
-        qs = torch.linspace(0, 1, nbins + 1, device=self.device)[1:-1]
-        edges = torch.quantile(Xs.to(torch.float32), qs, dim=0)  # [nb-1, f]
-        self.edges = edges.t().contiguous()                      # [f, nb-1]
+        if nan is None:
+            qs = torch.linspace(0, 1, nbins + 1, device=self.device)[1:-1]
+            edges = torch.quantile(Xs.to(torch.float32), qs, dim=0)
+            self.edges = edges.t().contiguous()                  # [f, nb-1]
+        else:
+            # the top code is the missing bin: nbins-1 bins for the real
+            # values, cut at the quantiles of each column's non-NaN values,
+            # and a closing +inf edge so that no real value passes it.  An
+            # all-NaN column (quantile = NaN) gets +inf everywhere.
+            self.missing_bin = nbins - 1
+            qs = torch.linspace(0, 1, nbins, device=self.device)[1:-1]
+            edges = torch.nanquantile(Xs.to(torch.float32), qs, dim=0)
+            edges = torch.where(torch.isnan(edges),
+                                torch.full_like(edges, float("inf")), edges)
+            self.edges = torch.cat(
+                [edges.t(), torch.full((self.f, 1), float("inf"),
+                                       device=self.device)],
+                dim=1).contiguous()                              # [f, nb-1]
+            # NaN cells are masked explicitly: bin a stand-in value, then
+            # overwrite their codes below
+            Xt = torch.where(nan, torch.zeros_like(Xt), Xt)
 
         # codes[n][fp]: count of edges < x  →  (code <= b) ⟺ (x <= edges[b])
         # row-major with the feature stride padded to a multiple of 4 so
@@ -409,6 +458,8 @@ class BinnedDataset:
         self.codes = torch.zeros(self.n, self.fp, dtype=torch.uint8,
                                  device=self.device)
         self.codes[:, : self.f] = codes_fm.to(torch.uint8).t()
+        if nan is not None:
+            self.codes[:, : self.f][nan] = self.missing_bin
         self.codes = self.codes.contiguous()
         del XT, Xt, Xs, codes_fm
 
@@ -471,6 +522,7 @@ class _NodeStore:
         self.left = np.empty(self.cap, dtype=np.int64)
         self.right = np.empty(self.cap, dtype=np.int64)
         self.leafrow = np.empty(self.cap, dtype=np.int64)
+        self.mleft = np.empty(self.cap, dtype=np.int64)
         self.tree_counts = np.zeros(TB, dtype=np.int64)
         self.leaf_blocks = []
         self.n_leaves = 0
@@ -482,7 +534,7 @@ class _NodeStore:
         while self.cap < need:
             self.cap *= 2
         for name in ("tree", "nid", "feature", "bin", "left", "right",
-                     "leafrow"):
+                     "leafrow", "mleft"):
             old = getattr(self, name)
             new = np.empty(self.cap, dtype=np.int64)
             new[: self.n] = old[: self.n]
@@ -501,6 +553,7 @@ class _NodeStore:
         self.left[sl] = -1
         self.right[sl] = -1
         self.leafrow[sl] = -1
+        self.mleft[sl] = 0
         return np.arange(lo, self.n)
 
     def make_leaves(self, rows, values):
@@ -547,9 +600,14 @@ class _NodeStore:
             left[leaf] = np.arange(leaf.sum())
             imp = importances[t]
             ssum = imp.sum()
+            # a dataset binned with allow_missing yields trees that carry
+            # the per-node direction of a missing value (0 at leaves)
+            mleft = (self.mleft[rows].astype(np.uint8)
+                     if ds.allow_missing else None)
             out.append(HistTree(
                 feature, thr, left, right, value, ds.classes_, ds.f,
-                (imp / ssum if ssum > 0 else imp).astype(np.float64)))
+                (imp / ssum if ssum > 0 else imp).astype(np.float64),
+                mleft))
         return out
 
 
@@ -575,6 +633,13 @@ class ForestBuilder:
         self.mid = float(min_impurity_decrease)
         self.m_features = resolve_max_features(max_features, ds.f)
         self.extra_mode = bool(extra_mode)
+        # the dataset reserved its top code for NaN: the split scan weighs
+        # both directions of that bin and the partition follows the winner
+        self.missing = ds.missing_bin is not None
+        if self.missing and self.extra_mode:
+            raise ValueError(
+                "extra_mode (random thresholds) is not supported on a "
+                "dataset with a missing bin")
         self.bootstrap = bool(bootstrap)
         self.tree_batch = int(tree_batch)
         self.subtract = bool(subtract)
@@ -690,9 +755,13 @@ class ForestBuilder:
                 weights, si_a, hist_nodes_cap, prev_hist=prev_hist,
                 fr_parent=fr_parent, fr_sib_start=fr_sib_start,
                 fr_sib_count=fr_sib_count, fr_left=fr_left)
-            (bfeat, bbin, bgain, bimp, bwl, pstats, lstats) = dec
+            (bfeat, bbin, bgain, bimp, bwl, pstats, lstats, bml) = dec
 
             wp = pstats.sum(axis=1) if ds.is_cls else pstats[:, 0]
+            if not self.missing:
+                # no missing bin in this dataset: a NaN met at predict time
+                # follows the majority of the split (ties to the right)
+                bml = (bwl + bwl > wp).astype(np.int64)
             counted = self.cnt_stat >= 0
             # min_samples_split compares row counts when the weights are
             # real numbers; the weight sums drive everything else
@@ -722,7 +791,7 @@ class ForestBuilder:
             nl = self._partition(
                 fr_tree[part_idx], fr_start[part_idx],
                 fr_count[part_idx], bfeat[part_idx], bbin[part_idx],
-                si_a, si_b)
+                bml[part_idx], si_a, si_b)
             si_a, si_b = si_b, si_a
 
             t_p = fr_tree[part_idx]
@@ -742,6 +811,7 @@ class ForestBuilder:
             pg = fr_grow[part_idx]
             st.feature[pg] = bfeat[part_idx]
             st.bin[pg] = bbin[part_idx]
+            st.mleft[pg] = bml[part_idx]
             st.left[pg] = lid
             st.right[pg] = rid
             np.add.at(
@@ -843,7 +913,7 @@ class ForestBuilder:
                          fr_left=None):
         """Per-frontier-node split decisions.
 
-        Returns (7-tuple of decision arrays, hist_or_None).  When the
+        Returns (8-tuple of decision arrays, hist_or_None).  When the
         previous level's histogram tensor is available (``prev_hist``,
         slot = previous frontier index) the HIP path uses the LightGBM
         subtraction trick: only the smaller child of each split parent is
@@ -983,11 +1053,14 @@ class ForestBuilder:
         S = ds.S
         seed_t = torch.as_tensor(node_seed.astype(np.int32), device=dev)
         # outputs packed into two buffers -> two D2H transfers per level
-        ibuf = torch.empty(2 * NF, dtype=torch.int32, device=dev)
+        # (the third int plane, the missing direction, is written in
+        # missing mode only)
+        ibuf = torch.empty(3 * NF, dtype=torch.int32, device=dev)
         fbuf = torch.empty((3 + 2 * S) * NF, dtype=torch.float32,
                            device=dev)
         out_feat = ibuf[:NF]
-        out_bin = ibuf[NF:]
+        out_bin = ibuf[NF: 2 * NF]
+        out_mleft = ibuf[2 * NF:]
         out_wl = fbuf[:NF]
         out_gain = fbuf[NF: 2 * NF]
         out_imp = fbuf[2 * NF: 3 * NF]
@@ -997,16 +1070,19 @@ class ForestBuilder:
             hist, seed_t, ds.f, ds.nbins, S, int(ds.is_cls), self.crit,
             self.m_features, int(self.extra_mode), self._msl_eff,
             out_feat, out_bin, out_wl, out_gain, out_imp, out_stats,
-            out_lstats, self.cnt_stat)
+            out_lstats, self.cnt_stat,
+            *((1, out_mleft) if self.missing else ()))
         ih = ibuf.cpu().numpy()
         fh = fbuf.cpu().numpy().astype(np.float64)
         return (ih[:NF].astype(np.int64),
-                ih[NF:].astype(np.int64),
+                ih[NF: 2 * NF].astype(np.int64),
                 fh[NF: 2 * NF],
                 fh[2 * NF: 3 * NF],
                 fh[:NF],
                 fh[3 * NF: (3 + S) * NF].reshape(NF, S),
-                fh[(3 + S) * NF:].reshape(NF, S))
+                fh[(3 + S) * NF:].reshape(NF, S),
+                ih[2 * NF:].astype(np.int64) if self.missing
+                else np.zeros(NF, dtype=np.int64))
 
     def _hist_and_split(self, seeds, fr_tree, fr_node, fr_start, fr_count,
                         weights, si, return_hist=False):
@@ -1042,6 +1118,7 @@ class ForestBuilder:
         bwl = np.zeros(NF)
         pstats = np.zeros((NF, S))
         lstats = np.zeros((NF, S))
+        bml = np.zeros(NF, dtype=np.int64)
         for k in range(NF):
             t = int(fr_tree[k])
             rows = si[t, int(fr_start[k]): int(fr_start[k] + fr_count[k])]
@@ -1077,8 +1154,8 @@ class ForestBuilder:
                                     f, -1).reshape(-1))
             res = self._split_eager(hist, int(node_seed[k]))
             (bfeat[k], bbin[k], bgain[k], bimp[k], bwl[k], pstats[k],
-             lstats[k]) = res
-        return bfeat, bbin, bgain, bimp, bwl, pstats, lstats
+             lstats[k], bml[k]) = res
+        return bfeat, bbin, bgain, bimp, bwl, pstats, lstats, bml
 
     def _split_eager(self, hist, seed):
         ds = self.ds
@@ -1095,47 +1172,55 @@ class ForestBuilder:
             sel = hv <= thresh
 
         cum = h.cumsum(axis=1)[:, :-1, :]              # left stats [f,nb-1,S]
-        if ds.is_cls:
-            wl = cum.sum(axis=2)
-        else:
-            wl = cum[:, :, 0]
-        wr = wp - wl
-        if ds.is_cls:
-            if self.crit == CRIT_GINI:
-                q = (cum ** 2).sum(axis=2)
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    imp_l = 1.0 - q / (wl * wl)
-                rq = ((parent[None, None, :] - cum) ** 2).sum(axis=2)
-                with np.errstate(divide="ignore", invalid="ignore"):
-                    imp_r = 1.0 - rq / (wr * wr)
+
+        def scan(cum):
+            """(wl, gain, valid) of the cuts whose left stats are ``cum``,
+            each [f, nbins-1]."""
+            if ds.is_cls:
+                wl = cum.sum(axis=2)
+            else:
+                wl = cum[:, :, 0]
+            wr = wp - wl
+            if ds.is_cls:
+                if self.crit == CRIT_GINI:
+                    q = (cum ** 2).sum(axis=2)
+                    with np.errstate(divide="ignore", invalid="ignore"):
+                        imp_l = 1.0 - q / (wl * wl)
+                    rq = ((parent[None, None, :] - cum) ** 2).sum(axis=2)
+                    with np.errstate(divide="ignore", invalid="ignore"):
+                        imp_r = 1.0 - rq / (wr * wr)
+                else:
+                    with np.errstate(divide="ignore", invalid="ignore"):
+                        pl = cum / wl[:, :, None]
+                        pr = (parent[None, None, :] - cum) / wr[:, :, None]
+                    imp_l = -np.nansum(
+                        np.where(pl > 0, pl * np.log2(pl, where=pl > 0),
+                                 0.0), axis=2)
+                    imp_r = -np.nansum(
+                        np.where(pr > 0, pr * np.log2(pr, where=pr > 0),
+                                 0.0), axis=2)
             else:
                 with np.errstate(divide="ignore", invalid="ignore"):
-                    pl = cum / wl[:, :, None]
-                    pr = (parent[None, None, :] - cum) / wr[:, :, None]
-                imp_l = -np.nansum(
-                    np.where(pl > 0, pl * np.log2(pl, where=pl > 0), 0.0),
-                    axis=2)
-                imp_r = -np.nansum(
-                    np.where(pr > 0, pr * np.log2(pr, where=pr > 0), 0.0),
-                    axis=2)
-        else:
-            with np.errstate(divide="ignore", invalid="ignore"):
-                ml = cum[:, :, 1] / wl
-                imp_l = np.maximum(cum[:, :, 2] / wl - ml * ml, 0.0)
-                mr = (parent[1] - cum[:, :, 1]) / wr
-                imp_r = np.maximum(
-                    (parent[2] - cum[:, :, 2]) / wr - mr * mr, 0.0)
-        with np.errstate(invalid="ignore"):
-            gain = imp_p - (wl * imp_l + wr * imp_r) / max(wp, 1e-30)
-        msl = self._msl_eff
-        if self.cnt_stat >= 0:
-            # k_tree_split_w: min-leaf on row counts, weight on both sides
-            cl = cum[:, :, self.cnt_stat]
-            cr = parent[self.cnt_stat] - cl
-            valid = ((cl >= msl) & (cr >= msl) & (wl > 0) & (wr > 0)
-                     & sel[:, None])
-        else:
-            valid = (wl >= msl) & (wr >= msl) & sel[:, None]
+                    ml = cum[:, :, 1] / wl
+                    imp_l = np.maximum(cum[:, :, 2] / wl - ml * ml, 0.0)
+                    mr = (parent[1] - cum[:, :, 1]) / wr
+                    imp_r = np.maximum(
+                        (parent[2] - cum[:, :, 2]) / wr - mr * mr, 0.0)
+            with np.errstate(invalid="ignore"):
+                gain = imp_p - (wl * imp_l + wr * imp_r) / max(wp, 1e-30)
+            msl = self._msl_eff
+            if self.cnt_stat >= 0:
+                # k_tree_split_w: min-leaf on row counts, weight on both
+                # sides
+                cl = cum[:, :, self.cnt_stat]
+                cr = parent[self.cnt_stat] - cl
+                valid = ((cl >= msl) & (cr >= msl) & (wl > 0) & (wr > 0)
+                         & sel[:, None])
+            else:
+                valid = (wl >= msl) & (wr >= msl) & sel[:, None]
+            return wl, gain, valid
+
+        wl, gain, valid = scan(cum)
         if self.extra_mode:
             extra_ok = np.zeros_like(valid)
             wbin = h.sum(axis=2) if ds.is_cls else h[:, :, 0]
@@ -1155,21 +1240,50 @@ class ForestBuilder:
                 extra_ok[j, rb] = True
             valid &= extra_ok
         gain = np.where(valid & np.isfinite(gain), gain, -1.0)
-        best = float(gain.max(initial=-1.0))
+        if not self.missing:
+            best = float(gain.max(initial=-1.0))
+            if best <= 0.0:
+                return (-1, -1, best, imp_p, 0.0, parent, np.zeros(S), 0)
+            cands = np.argwhere(gain >= best - 1e-12)
+            jf, jb = cands[np.lexsort((cands[:, 1], cands[:, 0]))][0]
+            return (int(jf), int(jb), float(gain[jf, jb]), imp_p,
+                    float(wl[jf, jb]), parent, cum[jf, jb].copy(), 0)
+
+        # missing mode (k_tree_split_m / _wm): the top bin holds the
+        # missing rows.  R candidates are the prefixes above (the missing
+        # bin stays right); L candidates add its stats to the left side,
+        # for the features whose missing bin holds weight in this node.
+        miss = h[:, nbins - 1, :]                      # [f, S]
+        wm = miss.sum(axis=1) if ds.is_cls else miss[:, 0]
+        cum_l = cum + miss[:, None, :]
+        wl_l, gain_l, valid_l = scan(cum_l)
+        valid_l &= (wm > 0)[:, None]
+        gain_l = np.where(valid_l & np.isfinite(gain_l), gain_l, -1.0)
+        both = np.stack([gain, gain_l], axis=2)        # [f, nb-1, (R, L)]
+        best = float(both.max(initial=-1.0))
         if best <= 0.0:
-            return (-1, -1, best, imp_p, 0.0, parent, np.zeros(S))
-        cands = np.argwhere(gain >= best - 1e-12)
-        jf, jb = cands[np.lexsort((cands[:, 1], cands[:, 0]))][0]
-        return (int(jf), int(jb), float(gain[jf, jb]), imp_p,
-                float(wl[jf, jb]), parent, cum[jf, jb].copy())
+            return (-1, -1, best, imp_p, 0.0, parent, np.zeros(S), 0)
+        # equal gains: lower feature, then lower bin, then R before L
+        cands = np.argwhere(both >= best - 1e-12)
+        jf, jb, jd = cands[np.lexsort(
+            (cands[:, 2], cands[:, 1], cands[:, 0]))][0]
+        if jd == 1:
+            return (int(jf), int(jb), float(gain_l[jf, jb]), imp_p,
+                    float(wl_l[jf, jb]), parent, cum_l[jf, jb].copy(), 1)
+        w_left = float(wl[jf, jb])
+        # nothing missing under this feature here: majority side
+        mleft = int(not wm[jf] > 0 and w_left + w_left > wp)
+        return (int(jf), int(jb), float(gain[jf, jb]), imp_p, w_left,
+                parent, cum[jf, jb].copy(), mleft)
 
     # -------------------------------------------------------------- #
     # partition (K3 count + host scan + K4 scatter, or eager)
     # -------------------------------------------------------------- #
-    def _partition(self, p_tree, p_start, p_count, p_feat, p_bin, si_in,
-                   si_out):
+    def _partition(self, p_tree, p_start, p_count, p_feat, p_bin, p_mleft,
+                   si_in, si_out):
         """Stable-partition each listed node's segment; returns per-node
-        left-row counts."""
+        left-row counts.  On a dataset with a missing bin a row goes left
+        iff ``code <= bin or (mleft and code == missing_bin)``."""
         ds = self.ds
         dev = ds.device
         NP = len(p_tree)
@@ -1179,7 +1293,10 @@ class ForestBuilder:
                 t = int(p_tree[k])
                 st, cnt = int(p_start[k]), int(p_count[k])
                 rows = si_in[t, st:st + cnt].to(torch.int64)
-                go_left = ds.codes[rows, int(p_feat[k])] <= int(p_bin[k])
+                code = ds.codes[rows, int(p_feat[k])]
+                go_left = code <= int(p_bin[k])
+                if self.missing and int(p_mleft[k]):
+                    go_left |= code == ds.missing_bin
                 lrows = rows[go_left]
                 rrows = rows[~go_left]
                 nl[k] = len(lrows)
@@ -1194,8 +1311,14 @@ class ForestBuilder:
         bin_t = torch.as_tensor(p_bin.astype(np.int32), device=dev)
         nch = len(chunks_np)
         counts = torch.empty(nch, dtype=torch.int32, device=dev)
+        # trailing arguments of the two partition entries in missing mode
+        miss_args = ()
+        if self.missing:
+            miss_args = (
+                torch.as_tensor(p_mleft.astype(np.int32), device=dev),
+                ds.missing_bin)
         self._ext.part_count(ds.codes, si_in, chunks, feat_t, bin_t,
-                             ds.n, counts)
+                             ds.n, counts, *miss_args)
         counts_np = counts.cpu().numpy().astype(np.int64)
 
         # per-node prefix over its chunks → absolute left/right bases
@@ -1217,7 +1340,7 @@ class ForestBuilder:
         lb = torch.as_tensor(lbase.astype(np.int32), device=dev)
         rb = torch.as_tensor(rbase.astype(np.int32), device=dev)
         self._ext.part_scatter(ds.codes, si_in, chunks, feat_t, bin_t,
-                               lb, rb, ds.n, si_out)
+                               lb, rb, ds.n, si_out, *miss_args)
         return nl
 
 
@@ -1231,14 +1354,24 @@ def _allow_eager():
 # flattened device forest (batched inference kernel)
 # --------------------------------------------------------------------- #
 
-def forest_walk(ext, op, xdev, *args):
+def forest_walk(ext, op, xdev, *args, mleft=None):
     """The one entry to the inference kernels: ``op`` is "predict" or
     "apply", ``xdev`` a device f32 ``[rows, f]`` block or a device CSR
-    ``(indptr, indices, data)``; ``args`` go on to the binding."""
+    ``(indptr, indices, data)``; ``args`` go on to the binding.  ``mleft``
+    (device uint8 per node, or None) selects the kernels that send a NaN
+    left where the flag is set; without it the call is the flag-free one."""
+    if mleft is not None:
+        args = args + (mleft,)
     if isinstance(xdev, tuple):
         getattr(ext, f"forest_{op}_csr")(*xdev, *args)
     else:
         getattr(ext, f"forest_{op}")(xdev, *args)
+
+
+def _missing_left_of(tree):
+    """A tree's per-node missing direction or None (trees pickled before
+    the attribute existed have none)."""
+    return getattr(tree, "missing_left", None)
 
 
 class FlatForest:
@@ -1258,6 +1391,7 @@ class FlatForest:
         self._ext = require_hip()
         self.device = torch.device(device)
         feats, thrs, lefts, rights, roots, vals = [], [], [], [], [], []
+        mlefts = []
         off = voff = 0
         for t in trees:
             internal = t.feature >= 0
@@ -1270,6 +1404,9 @@ class FlatForest:
             lefts.append(left)
             rights.append(right)
             vals.append(t.value)
+            ml = _missing_left_of(t)
+            mlefts.append(np.zeros(t.node_count, dtype=np.uint8)
+                          if ml is None else np.asarray(ml, dtype=np.uint8))
             roots.append(off)
             off += t.node_count
             voff += len(t.value)
@@ -1280,6 +1417,11 @@ class FlatForest:
         self.thr = as_t(thrs, torch.float32)
         self.left = as_t(lefts, torch.int32)
         self.right = as_t(rights, torch.int32)
+        # missing-direction flags ride along only when some tree has them;
+        # a forest without any takes the flag-free kernels
+        self.mleft = (
+            as_t(mlefts, torch.uint8)
+            if any(_missing_left_of(t) is not None for t in trees) else None)
         self.values = torch.as_tensor(
             np.ascontiguousarray(np.concatenate(vals, axis=0)),
             dtype=torch.float32, device=dev)
@@ -1325,7 +1467,8 @@ class FlatForest:
             out = torch.empty(rows, self.vs, dtype=torch.float32,
                               device=self.device)
             forest_walk(self._ext, "predict", xdev, self.feat, self.thr,
-                        self.left, self.right, self.roots, self.values, out)
+                        self.left, self.right, self.roots, self.values, out,
+                        mleft=self.mleft)
             outs.append(out.cpu().numpy())
         return np.concatenate(outs, axis=0)
 
@@ -1347,7 +1490,8 @@ class FlatForest:
             out = torch.empty(rows, self.n_trees, dtype=torch.int32,
                               device=self.device)
             forest_walk(self._ext, "apply", xdev, self.feat, self.thr,
-                        self.left, self.right, self.roots, out)
+                        self.left, self.right, self.roots, out,
+                        mleft=self.mleft)
             outs.append(out.cpu().numpy() - roots_np[None, :])
         return np.concatenate(outs, axis=0)
 
@@ -1374,11 +1518,15 @@ def _sklearn_tree_to_hist_tree(tree, kind):
     else:
         v = v.reshape(len(leaves), -1)[:, :1]
     left[leaves] = np.arange(len(leaves), dtype=np.int32)
+    # sklearn >= 1.3 learns, per split, the side a NaN goes to
+    mleft = getattr(t, "missing_go_to_left", None)
+    if mleft is not None:
+        mleft = np.ascontiguousarray(mleft, dtype=np.uint8)
     return HistTree(
         feature, threshold, left, right,
         np.ascontiguousarray(v, dtype=np.float32),
         getattr(tree, "classes_", None),
-        t.n_features, None,
+        t.n_features, None, mleft,
     )
 
 

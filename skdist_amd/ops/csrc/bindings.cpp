@@ -5,6 +5,8 @@
 
 #include <hip/hip_runtime.h>
 
+#include <optional>
+
 #include "tree_api.h"
 
 extern "C" hipError_t skdist_sgd_step(
@@ -500,6 +502,19 @@ int64_t rows_of(const torch::Tensor& out) {
     return out.dim() == 2 ? out.size(0) : -1;
 }
 
+// an optional trailing tensor: None and an empty tensor both mean "not
+// given" (the convention tree_hist uses for its absent tensors)
+using OptTensor = std::optional<torch::Tensor>;
+bool given(const OptTensor& t) { return t.has_value() && t->numel() > 0; }
+
+// per-node missing-direction flags of a flattened forest, uint8
+// [total_nodes]; returns the pointer a launcher takes (null = not given)
+const void* check_mleft(const OptTensor& mleft, const torch::Tensor& feat) {
+    if (!given(mleft)) return nullptr;
+    check_vec(*mleft, torch::kUInt8, feat.numel(), "mleft");
+    return mleft->data_ptr();
+}
+
 // the current stream, and a launcher's verdict as an exception
 hipStream_t cur_stream() { return c10::hip::getCurrentHIPStream().stream(); }
 void launched(hipError_t err, const char* what) {
@@ -549,14 +564,17 @@ void tree_hist(torch::Tensor codes, torch::Tensor y_int, torch::Tensor y_f,
         cur_stream()), "tree_hist");
 }
 
-// cnt_stat = -1: min-leaf on the weight sums; else on that (count) stat
+// cnt_stat = -1: min-leaf on the weight sums; else on that (count) stat.
+// missing != 0: bin nbins-1 is the missing bin; out_mleft int32 [NF] gets
+// the learned direction (1 = missing rows go left)
 void tree_split(torch::Tensor hist, torch::Tensor node_seed, int64_t f,
                 int64_t nbins, int64_t S, int64_t is_cls, int64_t crit,
                 int64_t m_features, int64_t extra_mode, double min_leaf,
                 torch::Tensor out_feat, torch::Tensor out_bin,
                 torch::Tensor out_wl, torch::Tensor out_gain,
                 torch::Tensor out_imp, torch::Tensor out_stats,
-                torch::Tensor out_lstats, int64_t cnt_stat) {
+                torch::Tensor out_lstats, int64_t cnt_stat, int64_t missing,
+                OptTensor out_mleft) {
     const int64_t NF = node_seed.numel();
     check_t(hist, torch::kFloat32, "hist");
     check_t(node_seed, torch::kInt32, "node_seed");
@@ -572,6 +590,15 @@ void tree_split(torch::Tensor hist, torch::Tensor node_seed, int64_t f,
                 "cnt_stat must be -1 or a stat index");
     TORCH_CHECK(f >= 1 && nbins >= 1 && NF < (1LL << 31) &&
                     hist.numel() >= NF * f * nbins * S, "hist too small");
+    TORCH_CHECK(missing == 0 || missing == 1, "missing must be 0 or 1");
+    TORCH_CHECK((missing != 0) == given(out_mleft) || NF == 0,
+                "out_mleft goes with missing = 1, and only with it");
+    if (missing) {
+        if (NF > 0) check_vec(*out_mleft, torch::kInt32, NF, "out_mleft");
+        TORCH_CHECK(nbins >= 2, "missing mode needs nbins >= 2");
+        TORCH_CHECK(extra_mode == 0,
+                    "missing mode has no extra_mode (random thresholds)");
+    }
     if (NF == 0) return;
     launched(skdist_tree_split(
         hist.data_ptr(), node_seed.data_ptr(), (int)NF, (int)f, (int)nbins,
@@ -579,43 +606,59 @@ void tree_split(torch::Tensor hist, torch::Tensor node_seed, int64_t f,
         (float)min_leaf, (int)cnt_stat, out_feat.data_ptr(),
         out_bin.data_ptr(), out_wl.data_ptr(), out_gain.data_ptr(),
         out_imp.data_ptr(), out_stats.data_ptr(), out_lstats.data_ptr(),
+        (int)missing, missing ? out_mleft->data_ptr() : nullptr,
         cur_stream()), "tree_split");
 }
 
-// split_feat / split_bin are indexed by the chunk table's part_slot
+// split_feat / split_bin / split_mleft are indexed by the chunk table's
+// part_slot; split_mleft (int32 [n_parts], optional) sends the rows whose
+// code is missing_code left as well
 int64_t check_part(const torch::Tensor& codes, const torch::Tensor& si,
                    const torch::Tensor& chunks,
                    const torch::Tensor& split_feat,
-                   const torch::Tensor& split_bin, int64_t n) {
+                   const torch::Tensor& split_bin,
+                   const OptTensor& split_mleft, int64_t missing_code,
+                   int64_t n) {
     check_codes(codes, n);
     check_plane(si, torch::kInt32, n, "sample_idx");
     check_t(split_feat, torch::kInt32, "split_feat");
     check_vec(split_bin, torch::kInt32, split_feat.numel(), "split_bin");
+    if (given(split_mleft)) {
+        check_vec(*split_mleft, torch::kInt32, split_feat.numel(),
+                  "split_mleft");
+        TORCH_CHECK(missing_code >= 0 && missing_code <= 255,
+                    "missing_code must be a uint8 code with split_mleft");
+    }
     return check_chunks(chunks);
 }
 
 void part_count(torch::Tensor codes, torch::Tensor sample_idx,
                 torch::Tensor chunks, torch::Tensor split_feat,
                 torch::Tensor split_bin, int64_t n,
-                torch::Tensor out_counts) {
-    const int64_t n_chunks =
-        check_part(codes, sample_idx, chunks, split_feat, split_bin, n);
+                torch::Tensor out_counts, OptTensor split_mleft,
+                int64_t missing_code) {
+    const int64_t n_chunks = check_part(codes, sample_idx, chunks,
+                                        split_feat, split_bin, split_mleft,
+                                        missing_code, n);
     check_vec(out_counts, torch::kInt32, n_chunks, "out_counts");
     if (n_chunks == 0) return;
     launched(skdist_part_count(
         codes.data_ptr(), sample_idx.data_ptr(), chunks.data_ptr(),
-        split_feat.data_ptr(), split_bin.data_ptr(), n,
-        (int)codes.size(1), (int)n_chunks, out_counts.data_ptr(),
-        cur_stream()), "part_count");
+        split_feat.data_ptr(), split_bin.data_ptr(),
+        given(split_mleft) ? split_mleft->data_ptr() : nullptr,
+        (int)missing_code, n, (int)codes.size(1), (int)n_chunks,
+        out_counts.data_ptr(), cur_stream()), "part_count");
 }
 
 void part_scatter(torch::Tensor codes, torch::Tensor sample_idx_in,
                   torch::Tensor chunks, torch::Tensor split_feat,
                   torch::Tensor split_bin, torch::Tensor left_base,
                   torch::Tensor right_base, int64_t n,
-                  torch::Tensor sample_idx_out) {
-    const int64_t n_chunks =
-        check_part(codes, sample_idx_in, chunks, split_feat, split_bin, n);
+                  torch::Tensor sample_idx_out, OptTensor split_mleft,
+                  int64_t missing_code) {
+    const int64_t n_chunks = check_part(codes, sample_idx_in, chunks,
+                                        split_feat, split_bin, split_mleft,
+                                        missing_code, n);
     check_2d(sample_idx_out, torch::kInt32, sample_idx_in.size(0), n,
              "sample_idx_out");
     check_vec(left_base, torch::kInt32, n_chunks, "left_base");
@@ -623,9 +666,11 @@ void part_scatter(torch::Tensor codes, torch::Tensor sample_idx_in,
     if (n_chunks == 0) return;
     launched(skdist_part_scatter(
         codes.data_ptr(), sample_idx_in.data_ptr(), chunks.data_ptr(),
-        split_feat.data_ptr(), split_bin.data_ptr(), left_base.data_ptr(),
-        right_base.data_ptr(), n, (int)codes.size(1), (int)n_chunks,
-        sample_idx_out.data_ptr(), cur_stream()), "part_scatter");
+        split_feat.data_ptr(), split_bin.data_ptr(),
+        given(split_mleft) ? split_mleft->data_ptr() : nullptr,
+        (int)missing_code, left_base.data_ptr(), right_base.data_ptr(), n,
+        (int)codes.size(1), (int)n_chunks, sample_idx_out.data_ptr(),
+        cur_stream()), "part_scatter");
 }
 
 // dense X [rows, f] f32; returns rows
@@ -639,28 +684,31 @@ int64_t check_dense_x(const torch::Tensor& X) {
 void forest_predict(torch::Tensor X, torch::Tensor feat, torch::Tensor thr,
                     torch::Tensor left, torch::Tensor right,
                     torch::Tensor roots, torch::Tensor values,
-                    torch::Tensor out) {
+                    torch::Tensor out, OptTensor mleft) {
     const int64_t rows = check_dense_x(X);
     check_nodes(feat, thr, left, right, roots);
+    const void* ml = check_mleft(mleft, feat);
     const int64_t vs = check_payload(values, out, rows);
     if (rows == 0) return;
     launched(skdist_forest_predict(
         X.data_ptr(), feat.data_ptr(), thr.data_ptr(), left.data_ptr(),
-        right.data_ptr(), roots.data_ptr(), values.data_ptr(),
+        right.data_ptr(), roots.data_ptr(), values.data_ptr(), ml,
         out.data_ptr(), rows, (int)X.size(1), (int)roots.numel(), (int)vs,
         cur_stream()), "forest_predict");
 }
 
 void forest_apply(torch::Tensor X, torch::Tensor feat, torch::Tensor thr,
                   torch::Tensor left, torch::Tensor right,
-                  torch::Tensor roots, torch::Tensor out_leaf) {
+                  torch::Tensor roots, torch::Tensor out_leaf,
+                  OptTensor mleft) {
     const int64_t rows = check_dense_x(X);
     check_nodes(feat, thr, left, right, roots);
+    const void* ml = check_mleft(mleft, feat);
     check_2d(out_leaf, torch::kInt32, rows, roots.numel(), "out_leaf");
     if (rows == 0) return;
     launched(skdist_forest_apply(
         X.data_ptr(), feat.data_ptr(), thr.data_ptr(), left.data_ptr(),
-        right.data_ptr(), roots.data_ptr(), out_leaf.data_ptr(), rows,
+        right.data_ptr(), roots.data_ptr(), ml, out_leaf.data_ptr(), rows,
         (int)X.size(1), (int)roots.numel(), cur_stream()), "forest_apply");
 }
 
@@ -668,16 +716,18 @@ void forest_predict_csr(torch::Tensor indptr, torch::Tensor indices,
                         torch::Tensor data, torch::Tensor feat,
                         torch::Tensor thr, torch::Tensor left,
                         torch::Tensor right, torch::Tensor roots,
-                        torch::Tensor values, torch::Tensor out) {
+                        torch::Tensor values, torch::Tensor out,
+                        OptTensor mleft) {
     const int64_t rows = rows_of(out);
     check_csr(indptr, indices, data, rows);
     check_nodes(feat, thr, left, right, roots);
+    const void* ml = check_mleft(mleft, feat);
     const int64_t vs = check_payload(values, out, rows);
     if (rows == 0) return;
     launched(skdist_forest_predict_csr(
         indptr.data_ptr(), indices.data_ptr(), data.data_ptr(),
         feat.data_ptr(), thr.data_ptr(), left.data_ptr(),
-        right.data_ptr(), roots.data_ptr(), values.data_ptr(),
+        right.data_ptr(), roots.data_ptr(), values.data_ptr(), ml,
         out.data_ptr(), rows, indices.numel(), (int)roots.numel(),
         (int)vs, cur_stream()), "forest_predict_csr");
 }
@@ -686,16 +736,17 @@ void forest_apply_csr(torch::Tensor indptr, torch::Tensor indices,
                       torch::Tensor data, torch::Tensor feat,
                       torch::Tensor thr, torch::Tensor left,
                       torch::Tensor right, torch::Tensor roots,
-                      torch::Tensor out_leaf) {
+                      torch::Tensor out_leaf, OptTensor mleft) {
     const int64_t rows = rows_of(out_leaf);
     check_csr(indptr, indices, data, rows);
     check_nodes(feat, thr, left, right, roots);
+    const void* ml = check_mleft(mleft, feat);
     check_2d(out_leaf, torch::kInt32, rows, roots.numel(), "out_leaf");
     if (rows == 0) return;
     launched(skdist_forest_apply_csr(
         indptr.data_ptr(), indices.data_ptr(), data.data_ptr(),
         feat.data_ptr(), thr.data_ptr(), left.data_ptr(),
-        right.data_ptr(), roots.data_ptr(), out_leaf.data_ptr(), rows,
+        right.data_ptr(), roots.data_ptr(), ml, out_leaf.data_ptr(), rows,
         indices.numel(), (int)roots.numel(), cur_stream()),
         "forest_apply_csr");
 }
@@ -839,16 +890,50 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("tree_hist", &tree_hist,
           "per-(node,feature,bin) stats: class counts, (w,wy,wyy), or "
           "(W,Wy,Wyy,C) with f32 row weights");
+    // the trailing arguments with defaults are the missing-value ones;
+    // every entry keeps its earlier positional argument list
+    namespace py = pybind11;
     m.def("tree_split", &tree_split,
           "best split per frontier node; min-leaf on the weight sums "
-          "(cnt_stat = -1) or on a count stat");
-    m.def("part_count", &part_count, "partition phase A: left counts");
-    m.def("part_scatter", &part_scatter, "partition phase B: scatter");
-    m.def("forest_predict", &forest_predict, "batched forest inference");
-    m.def("forest_apply", &forest_apply, "leaf ids per (row, tree)");
+          "(cnt_stat = -1) or on a count stat; missing = 1 scans both "
+          "directions of the missing bin nbins-1 and fills out_mleft",
+          py::arg("hist"), py::arg("node_seed"), py::arg("f"),
+          py::arg("nbins"), py::arg("S"), py::arg("is_cls"),
+          py::arg("crit"), py::arg("m_features"), py::arg("extra_mode"),
+          py::arg("min_leaf"), py::arg("out_feat"), py::arg("out_bin"),
+          py::arg("out_wl"), py::arg("out_gain"), py::arg("out_imp"),
+          py::arg("out_stats"), py::arg("out_lstats"), py::arg("cnt_stat"),
+          py::arg("missing") = 0, py::arg("out_mleft") = py::none());
+    m.def("part_count", &part_count, "partition phase A: left counts",
+          py::arg("codes"), py::arg("sample_idx"), py::arg("chunks"),
+          py::arg("split_feat"), py::arg("split_bin"), py::arg("n"),
+          py::arg("out_counts"), py::arg("split_mleft") = py::none(),
+          py::arg("missing_code") = -1);
+    m.def("part_scatter", &part_scatter, "partition phase B: scatter",
+          py::arg("codes"), py::arg("sample_idx_in"), py::arg("chunks"),
+          py::arg("split_feat"), py::arg("split_bin"),
+          py::arg("left_base"), py::arg("right_base"), py::arg("n"),
+          py::arg("sample_idx_out"), py::arg("split_mleft") = py::none(),
+          py::arg("missing_code") = -1);
+    m.def("forest_predict", &forest_predict, "batched forest inference",
+          py::arg("X"), py::arg("feat"), py::arg("thr"), py::arg("left"),
+          py::arg("right"), py::arg("roots"), py::arg("values"),
+          py::arg("out"), py::arg("mleft") = py::none());
+    m.def("forest_apply", &forest_apply, "leaf ids per (row, tree)",
+          py::arg("X"), py::arg("feat"), py::arg("thr"), py::arg("left"),
+          py::arg("right"), py::arg("roots"), py::arg("out_leaf"),
+          py::arg("mleft") = py::none());
     m.def("forest_predict_csr", &forest_predict_csr,
-          "batched forest inference over CSR rows");
+          "batched forest inference over CSR rows", py::arg("indptr"),
+          py::arg("indices"), py::arg("data"), py::arg("feat"),
+          py::arg("thr"), py::arg("left"), py::arg("right"),
+          py::arg("roots"), py::arg("values"), py::arg("out"),
+          py::arg("mleft") = py::none());
     m.def("forest_apply_csr", &forest_apply_csr,
-          "leaf ids per (row, tree) over CSR rows");
+          "leaf ids per (row, tree) over CSR rows", py::arg("indptr"),
+          py::arg("indices"), py::arg("data"), py::arg("feat"),
+          py::arg("thr"), py::arg("left"), py::arg("right"),
+          py::arg("roots"), py::arg("out_leaf"),
+          py::arg("mleft") = py::none());
     m.def("bin_csr", &bin_csr, "CSR -> uint8 quantile codes");
 }

@@ -7,8 +7,9 @@
 // walks all trees for one row, accumulating leaf payloads in registers.
 //
 // There is ONE walk (descend) and ONE predict / apply body, templated on a
-// row accessor with a single `float at(int jf)`; the four kernels are
-// predict/apply x dense/CSR instantiations of them.  One thread per row and
+// row accessor with a single `float at(int jf)` and on a bool MISS (NaN
+// follows a per-node direction flag); the eight kernels are predict/apply
+// x dense/CSR x MISS instantiations of them.  One thread per row and
 // trees in order t = 0..T-1, so the accumulation order — and therefore
 // every output bit — is the same for a CSR row and for its dense copy.
 //
@@ -19,6 +20,7 @@
 //   left/right [total_nodes] int32 (absolute node ids, pre-offset per tree)
 //   roots   [n_trees] int32
 //   values  [n_values][vs] f32
+//   mleft   [total_nodes] uint8   (MISS kernels: 1 = NaN goes left here)
 //
 // CSR rows (scipy-sparse X, never densified):
 //   indptr  [rows+1] int64   (rebased so indptr[0] == 0 for the chunk)
@@ -69,34 +71,42 @@ struct CsrRow {
     }
 };
 
-// root-to-leaf descent of tree t; returns the leaf's node id
-template <typename Row>
+// root-to-leaf descent of tree t; returns the leaf's node id.
+// MISS: a NaN value (x <= thr is false for it) goes left at the nodes whose
+// mleft flag is set; without MISS mleft is not read and NaN goes right.
+template <bool MISS, typename Row>
 static __device__ __forceinline__ int descend(
     const Row& row, const int* __restrict__ feat,
     const float* __restrict__ thr, const int* __restrict__ left,
-    const int* __restrict__ right, const int* __restrict__ roots, int t) {
+    const int* __restrict__ right, const int* __restrict__ roots,
+    const unsigned char* __restrict__ mleft, int t) {
     int node = roots[t];
     int jf = feat[node];
     while (jf >= 0) {
-        node = (row.at(jf) <= thr[node]) ? left[node] : right[node];
+        const float x = row.at(jf);
+        bool go_left = x <= thr[node];
+        if (MISS) go_left = go_left || (x != x && mleft[node] != 0);
+        node = go_left ? left[node] : right[node];
         jf = feat[node];
     }
     return node;
 }
 
 // mean leaf payload over the trees -> out[r][0..vs)
-template <typename Row>
+template <bool MISS, typename Row>
 static __device__ __forceinline__ void predict_row(
     const Row& row, const int* __restrict__ feat,
     const float* __restrict__ thr, const int* __restrict__ left,
     const int* __restrict__ right, const int* __restrict__ roots,
-    const float* __restrict__ values, float* __restrict__ out, long long r,
-    int n_trees, int vs) {
+    const float* __restrict__ values,
+    const unsigned char* __restrict__ mleft, float* __restrict__ out,
+    long long r, int n_trees, int vs) {
     float acc[MAXVS];
 #pragma unroll
     for (int c = 0; c < MAXVS; ++c) acc[c] = 0.f;
     for (int t = 0; t < n_trees; ++t) {
-        const int node = descend(row, feat, thr, left, right, roots, t);
+        const int node =
+            descend<MISS>(row, feat, thr, left, right, roots, mleft, t);
         const float* v = values + (long long)left[node] * vs;
 #pragma unroll
         for (int c = 0; c < MAXVS; ++c)
@@ -109,68 +119,97 @@ static __device__ __forceinline__ void predict_row(
 }
 
 // leaf node id per tree -> out_leaf[r][0..n_trees)
-template <typename Row>
+template <bool MISS, typename Row>
 static __device__ __forceinline__ void apply_row(
     const Row& row, const int* __restrict__ feat,
     const float* __restrict__ thr, const int* __restrict__ left,
     const int* __restrict__ right, const int* __restrict__ roots,
-    int* __restrict__ out_leaf, long long r, int n_trees) {
+    const unsigned char* __restrict__ mleft, int* __restrict__ out_leaf,
+    long long r, int n_trees) {
     for (int t = 0; t < n_trees; ++t)
         out_leaf[r * n_trees + t] =
-            descend(row, feat, thr, left, right, roots, t);
+            descend<MISS>(row, feat, thr, left, right, roots, mleft, t);
 }
 
-extern "C" __global__ __launch_bounds__(256) void k_forest_predict(
-    const float* __restrict__ X, const int* __restrict__ feat,
-    const float* __restrict__ thr, const int* __restrict__ left,
-    const int* __restrict__ right, const int* __restrict__ roots,
-    const float* __restrict__ values, float* __restrict__ out,
-    long long rows, int f, int n_trees, int vs) {
-    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= rows) return;
-    predict_row(DenseRow(X, r, f), feat, thr, left, right, roots, values,
-                out, r, n_trees, vs);
-}
+// The eight kernels: {predict, apply} x {dense, CSR} x {plain, _m}.  The
+// plain ones are the MISS = false instantiations and take no mleft.
+#define FOREST_PREDICT_KERNEL(NAME, MISS, MLEFT_PARAM, MLEFT)               \
+    extern "C" __global__ __launch_bounds__(256) void NAME(                 \
+        const float* __restrict__ X, const int* __restrict__ feat,          \
+        const float* __restrict__ thr, const int* __restrict__ left,        \
+        const int* __restrict__ right, const int* __restrict__ roots,       \
+        const float* __restrict__ values, MLEFT_PARAM                       \
+        float* __restrict__ out, long long rows, int f, int n_trees,        \
+        int vs) {                                                           \
+        const long long r =                                                 \
+            (long long)blockIdx.x * blockDim.x + threadIdx.x;               \
+        if (r >= rows) return;                                              \
+        predict_row<MISS>(DenseRow(X, r, f), feat, thr, left, right, roots, \
+                          values, MLEFT, out, r, n_trees, vs);              \
+    }
 
-extern "C" __global__ __launch_bounds__(256) void k_forest_apply(
-    const float* __restrict__ X, const int* __restrict__ feat,
-    const float* __restrict__ thr, const int* __restrict__ left,
-    const int* __restrict__ right, const int* __restrict__ roots,
-    int* __restrict__ out_leaf, long long rows, int f, int n_trees) {
-    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= rows) return;
-    apply_row(DenseRow(X, r, f), feat, thr, left, right, roots, out_leaf, r,
-              n_trees);
-}
+#define FOREST_APPLY_KERNEL(NAME, MISS, MLEFT_PARAM, MLEFT)                 \
+    extern "C" __global__ __launch_bounds__(256) void NAME(                 \
+        const float* __restrict__ X, const int* __restrict__ feat,          \
+        const float* __restrict__ thr, const int* __restrict__ left,        \
+        const int* __restrict__ right, const int* __restrict__ roots,       \
+        MLEFT_PARAM int* __restrict__ out_leaf, long long rows, int f,      \
+        int n_trees) {                                                      \
+        const long long r =                                                 \
+            (long long)blockIdx.x * blockDim.x + threadIdx.x;               \
+        if (r >= rows) return;                                              \
+        apply_row<MISS>(DenseRow(X, r, f), feat, thr, left, right, roots,   \
+                        MLEFT, out_leaf, r, n_trees);                       \
+    }
 
-extern "C" __global__ __launch_bounds__(256) void k_forest_predict_csr(
-    const long long* __restrict__ indptr, const int* __restrict__ indices,
-    const float* __restrict__ data, const int* __restrict__ feat,
-    const float* __restrict__ thr, const int* __restrict__ left,
-    const int* __restrict__ right, const int* __restrict__ roots,
-    const float* __restrict__ values, float* __restrict__ out,
-    long long rows, long long nnz, int n_trees, int vs) {
-    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= rows) return;
-    predict_row(CsrRow(indptr, indices, data, r, nnz), feat, thr, left,
-                right, roots, values, out, r, n_trees, vs);
-}
+#define FOREST_PREDICT_CSR_KERNEL(NAME, MISS, MLEFT_PARAM, MLEFT)           \
+    extern "C" __global__ __launch_bounds__(256) void NAME(                 \
+        const long long* __restrict__ indptr,                               \
+        const int* __restrict__ indices, const float* __restrict__ data,    \
+        const int* __restrict__ feat, const float* __restrict__ thr,        \
+        const int* __restrict__ left, const int* __restrict__ right,        \
+        const int* __restrict__ roots, const float* __restrict__ values,    \
+        MLEFT_PARAM float* __restrict__ out, long long rows,                \
+        long long nnz, int n_trees, int vs) {                               \
+        const long long r =                                                 \
+            (long long)blockIdx.x * blockDim.x + threadIdx.x;               \
+        if (r >= rows) return;                                              \
+        predict_row<MISS>(CsrRow(indptr, indices, data, r, nnz), feat, thr, \
+                          left, right, roots, values, MLEFT, out, r,        \
+                          n_trees, vs);                                     \
+    }
 
-extern "C" __global__ __launch_bounds__(256) void k_forest_apply_csr(
-    const long long* __restrict__ indptr, const int* __restrict__ indices,
-    const float* __restrict__ data, const int* __restrict__ feat,
-    const float* __restrict__ thr, const int* __restrict__ left,
-    const int* __restrict__ right, const int* __restrict__ roots,
-    int* __restrict__ out_leaf, long long rows, long long nnz,
-    int n_trees) {
-    const long long r = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (r >= rows) return;
-    apply_row(CsrRow(indptr, indices, data, r, nnz), feat, thr, left, right,
-              roots, out_leaf, r, n_trees);
-}
+#define FOREST_APPLY_CSR_KERNEL(NAME, MISS, MLEFT_PARAM, MLEFT)             \
+    extern "C" __global__ __launch_bounds__(256) void NAME(                 \
+        const long long* __restrict__ indptr,                               \
+        const int* __restrict__ indices, const float* __restrict__ data,    \
+        const int* __restrict__ feat, const float* __restrict__ thr,        \
+        const int* __restrict__ left, const int* __restrict__ right,        \
+        const int* __restrict__ roots, MLEFT_PARAM                          \
+        int* __restrict__ out_leaf, long long rows, long long nnz,          \
+        int n_trees) {                                                      \
+        const long long r =                                                 \
+            (long long)blockIdx.x * blockDim.x + threadIdx.x;               \
+        if (r >= rows) return;                                              \
+        apply_row<MISS>(CsrRow(indptr, indices, data, r, nnz), feat, thr,   \
+                        left, right, roots, MLEFT, out_leaf, r, n_trees);   \
+    }
+
+#define NO_MLEFT_PARAM
+#define MLEFT_PARAM_ const unsigned char* __restrict__ mleft,
+FOREST_PREDICT_KERNEL(k_forest_predict, false, NO_MLEFT_PARAM, nullptr)
+FOREST_PREDICT_KERNEL(k_forest_predict_m, true, MLEFT_PARAM_, mleft)
+FOREST_APPLY_KERNEL(k_forest_apply, false, NO_MLEFT_PARAM, nullptr)
+FOREST_APPLY_KERNEL(k_forest_apply_m, true, MLEFT_PARAM_, mleft)
+FOREST_PREDICT_CSR_KERNEL(k_forest_predict_csr, false, NO_MLEFT_PARAM,
+                          nullptr)
+FOREST_PREDICT_CSR_KERNEL(k_forest_predict_csr_m, true, MLEFT_PARAM_, mleft)
+FOREST_APPLY_CSR_KERNEL(k_forest_apply_csr, false, NO_MLEFT_PARAM, nullptr)
+FOREST_APPLY_CSR_KERNEL(k_forest_apply_csr_m, true, MLEFT_PARAM_, mleft)
 
 // ---------------------------------------------------------------------- //
-// C launchers: one thread per row, block 256
+// C launchers: one thread per row, block 256; mleft != nullptr picks the
+// MISS instantiation
 // ---------------------------------------------------------------------- //
 static inline dim3 row_grid(long long rows) {
     return dim3((unsigned)((rows + 255) / 256));
@@ -178,61 +217,100 @@ static inline dim3 row_grid(long long rows) {
 
 extern "C" hipError_t skdist_forest_predict(
     const void* X, const void* feat, const void* thr, const void* left,
-    const void* right, const void* roots, const void* values, void* out,
-    long long rows, int f, int n_trees, int vs, hipStream_t stream) {
+    const void* right, const void* roots, const void* values,
+    const void* mleft, void* out, long long rows, int f, int n_trees,
+    int vs, hipStream_t stream) {
     if (vs > MAXVS) return hipErrorInvalidValue;
     if (rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_forest_predict, row_grid(rows), dim3(256), 0,
-                       stream, (const float*)X, (const int*)feat,
-                       (const float*)thr, (const int*)left,
-                       (const int*)right, (const int*)roots,
-                       (const float*)values, (float*)out, rows, f, n_trees,
-                       vs);
+    if (mleft != nullptr)
+        hipLaunchKernelGGL(k_forest_predict_m, row_grid(rows), dim3(256), 0,
+                           stream, (const float*)X, (const int*)feat,
+                           (const float*)thr, (const int*)left,
+                           (const int*)right, (const int*)roots,
+                           (const float*)values,
+                           (const unsigned char*)mleft, (float*)out, rows,
+                           f, n_trees, vs);
+    else
+        hipLaunchKernelGGL(k_forest_predict, row_grid(rows), dim3(256), 0,
+                           stream, (const float*)X, (const int*)feat,
+                           (const float*)thr, (const int*)left,
+                           (const int*)right, (const int*)roots,
+                           (const float*)values, (float*)out, rows, f,
+                           n_trees, vs);
     return hipGetLastError();
 }
 
 extern "C" hipError_t skdist_forest_apply(
     const void* X, const void* feat, const void* thr, const void* left,
-    const void* right, const void* roots, void* out_leaf, long long rows,
-    int f, int n_trees, hipStream_t stream) {
+    const void* right, const void* roots, const void* mleft,
+    void* out_leaf, long long rows, int f, int n_trees,
+    hipStream_t stream) {
     if (rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_forest_apply, row_grid(rows), dim3(256), 0, stream,
-                       (const float*)X, (const int*)feat,
-                       (const float*)thr, (const int*)left,
-                       (const int*)right, (const int*)roots,
-                       (int*)out_leaf, rows, f, n_trees);
+    if (mleft != nullptr)
+        hipLaunchKernelGGL(k_forest_apply_m, row_grid(rows), dim3(256), 0,
+                           stream, (const float*)X, (const int*)feat,
+                           (const float*)thr, (const int*)left,
+                           (const int*)right, (const int*)roots,
+                           (const unsigned char*)mleft, (int*)out_leaf,
+                           rows, f, n_trees);
+    else
+        hipLaunchKernelGGL(k_forest_apply, row_grid(rows), dim3(256), 0,
+                           stream, (const float*)X, (const int*)feat,
+                           (const float*)thr, (const int*)left,
+                           (const int*)right, (const int*)roots,
+                           (int*)out_leaf, rows, f, n_trees);
     return hipGetLastError();
 }
 
 extern "C" hipError_t skdist_forest_predict_csr(
     const void* indptr, const void* indices, const void* data,
     const void* feat, const void* thr, const void* left, const void* right,
-    const void* roots, const void* values, void* out, long long rows,
-    long long nnz, int n_trees, int vs, hipStream_t stream) {
+    const void* roots, const void* values, const void* mleft, void* out,
+    long long rows, long long nnz, int n_trees, int vs,
+    hipStream_t stream) {
     if (vs > MAXVS) return hipErrorInvalidValue;
     if (rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_forest_predict_csr, row_grid(rows), dim3(256), 0,
-                       stream, (const long long*)indptr,
-                       (const int*)indices, (const float*)data,
-                       (const int*)feat, (const float*)thr,
-                       (const int*)left, (const int*)right,
-                       (const int*)roots, (const float*)values,
-                       (float*)out, rows, nnz, n_trees, vs);
+    if (mleft != nullptr)
+        hipLaunchKernelGGL(k_forest_predict_csr_m, row_grid(rows),
+                           dim3(256), 0, stream, (const long long*)indptr,
+                           (const int*)indices, (const float*)data,
+                           (const int*)feat, (const float*)thr,
+                           (const int*)left, (const int*)right,
+                           (const int*)roots, (const float*)values,
+                           (const unsigned char*)mleft, (float*)out, rows,
+                           nnz, n_trees, vs);
+    else
+        hipLaunchKernelGGL(k_forest_predict_csr, row_grid(rows), dim3(256),
+                           0, stream, (const long long*)indptr,
+                           (const int*)indices, (const float*)data,
+                           (const int*)feat, (const float*)thr,
+                           (const int*)left, (const int*)right,
+                           (const int*)roots, (const float*)values,
+                           (float*)out, rows, nnz, n_trees, vs);
     return hipGetLastError();
 }
 
 extern "C" hipError_t skdist_forest_apply_csr(
     const void* indptr, const void* indices, const void* data,
     const void* feat, const void* thr, const void* left, const void* right,
-    const void* roots, void* out_leaf, long long rows, long long nnz,
-    int n_trees, hipStream_t stream) {
+    const void* roots, const void* mleft, void* out_leaf, long long rows,
+    long long nnz, int n_trees, hipStream_t stream) {
     if (rows <= 0) return hipSuccess;
-    hipLaunchKernelGGL(k_forest_apply_csr, row_grid(rows), dim3(256), 0,
-                       stream, (const long long*)indptr,
-                       (const int*)indices, (const float*)data,
-                       (const int*)feat, (const float*)thr,
-                       (const int*)left, (const int*)right,
-                       (const int*)roots, (int*)out_leaf, rows, nnz,
-                       n_trees);
+    if (mleft != nullptr)
+        hipLaunchKernelGGL(k_forest_apply_csr_m, row_grid(rows), dim3(256),
+                           0, stream, (const long long*)indptr,
+                           (const int*)indices, (const float*)data,
+                           (const int*)feat, (const float*)thr,
+                           (const int*)left, (const int*)right,
+                           (const int*)roots, (const unsigned char*)mleft,
+                           (int*)out_leaf, rows, nnz, n_trees);
+    else
+        hipLaunchKernelGGL(k_forest_apply_csr, row_grid(rows), dim3(256), 0,
+                           stream, (const long long*)indptr,
+                           (const int*)indices, (const float*)data,
+                           (const int*)feat, (const float*)thr,
+                           (const int*)left, (const int*)right,
+                           (const int*)roots, (int*)out_leaf, rows, nnz,
+                           n_trees);
     return hipGetLastError();
 }

@@ -17,9 +17,16 @@
 //   K4 k_part_scatter: stable partition of each node's sample segment
 //
 // K1 and K2 have ONE body each (tree_hist_body<ROW_W>,
-// tree_split_body<COUNTED>) behind the paired kernel names, and ONE checked
-// launcher each (tree_api.h) that picks the instantiation: skdist_tree_hist
-// by row_w != nullptr, skdist_tree_split by cnt_stat >= 0.
+// tree_split_body<COUNTED, MISSING>) behind the kernel names, and ONE
+// checked launcher each (tree_api.h) that picks the instantiation:
+// skdist_tree_hist by row_w != nullptr, skdist_tree_split by cnt_stat >= 0
+// and by its `missing` flag.
+//
+// Missing values: a dataset binned with a missing bin keeps code nbins-1
+// for NaN cells.  K1 is unchanged (missing is one more bin); the MISSING
+// split scan evaluates every (feature, bin) cut twice, with the missing
+// bin's stats on the right (R) and on the left (L), and reports the learned
+// direction per node; K3/K4 send code nbins-1 left where that flag is set.
 //
 // Host orchestration + torch eager reference: skdist_amd/models/forest.py.
 //
@@ -216,7 +223,39 @@ impurity(const float* s, float w, int S, int is_cls, int crit) {
 // numbers — the min-leaf test reads the integer-valued stat cnt_stat
 // instead of the weight sums, and a candidate also needs weight on both
 // sides.  Impurity, gain, tie-break and outputs are the same either way.
+//
+// MISSING: the top bin nbins-1 holds the rows whose feature value is
+// missing.  Candidates are (feature, bin b <= nbins-2, direction): R is the
+// plain prefix (the missing bin is the top bin, so it is already on the
+// right; b = nbins-2 cuts "all present | all missing"), L adds the missing
+// bin's stats to the left side.  L is scanned only where the feature's
+// missing bin holds weight in this node; elsewhere the direction is the
+// majority side (wl > wr, ties to the right).  Order among equal gains:
+// lower feature, lower bin, R before L.  Validity, impurity and gain are
+// the non-MISSING ones.
 template <bool COUNTED>
+static __device__ __forceinline__ bool split_candidate(
+    const float* left, float wl, const float* s_parent, float wp,
+    float imp_p, int S, int is_cls, int crit, float min_leaf_w, int cnt_stat,
+    float* gain_out) {
+    const float wr = wp - wl;
+    if (COUNTED) {
+        const float cl = left[cnt_stat];
+        const float cr = s_parent[cnt_stat] - cl;
+        if (cl < min_leaf_w || cr < min_leaf_w) return false;
+        if (!(wl > 0.f && wr > 0.f)) return false;
+    } else {
+        if (wl < min_leaf_w || wr < min_leaf_w) return false;
+    }
+    const float imp_l = impurity(left, wl, S, is_cls, crit);
+    float right[36];
+    for (int c = 0; c < S; ++c) right[c] = s_parent[c] - left[c];
+    const float imp_r = impurity(right, wr, S, is_cls, crit);
+    *gain_out = imp_p - (wl * imp_l + wr * imp_r) / wp;
+    return true;
+}
+
+template <bool COUNTED, bool MISSING>
 static __device__ __forceinline__ void tree_split_body(
     const float* __restrict__ hist,        // [NF][f][nbins][S]
     const unsigned* __restrict__ node_seed,  // [NF]
@@ -229,7 +268,8 @@ static __device__ __forceinline__ void tree_split_body(
     float* __restrict__ out_imp,  // [NF]  parent impurity
     float* __restrict__ out_stats,  // [NF][S] parent stat totals
     float* __restrict__ out_lstats, // [NF][S] winning split's left stats
-    int cnt_stat) {
+    int cnt_stat,
+    int* __restrict__ out_mleft) {  // [NF] (MISSING) 1 = missing rows go left
     const int node = blockIdx.x;
     const unsigned seed = node_seed[node];
     const float* H = hist + (long long)node * f * nbins * S;
@@ -241,6 +281,7 @@ static __device__ __forceinline__ void tree_split_body(
     __shared__ int s_best_feat[256 / WAVE];
     __shared__ int s_best_bin[256 / WAVE];
     __shared__ float s_best_wl[256 / WAVE];
+    __shared__ int s_best_ml[MISSING ? 256 / WAVE : 1];
 
     // parent totals from feature 0's histogram
     for (int c = tid; c < S; c += blockDim.x) s_parent[c] = 0.f;
@@ -283,7 +324,10 @@ static __device__ __forceinline__ void tree_split_body(
     float best_gain = -1.f;
     int best_feat = -1, best_bin = -1;
     float best_wl = 0.f;
+    int best_ml = 0;
     float left[36];
+    float miss[MISSING ? 36 : 1];   // the feature's missing-bin stats
+    float lm[MISSING ? 36 : 1];     // left + miss: the L candidate
     for (int j = tid; j < f; j += blockDim.x) {
         if (m_features < f &&
             wang_hash(seed ^ (unsigned)(j * 2654435761u)) > h_thresh)
@@ -312,6 +356,16 @@ static __device__ __forceinline__ void tree_split_body(
         }
         for (int c = 0; c < S; ++c) left[c] = 0.f;
         float wl = 0.f;
+        float wm = 0.f;
+        if (MISSING) {
+            // read once per feature, not per bin
+            for (int c = 0; c < S; ++c) miss[c] = Hj[(nbins - 1) * S + c];
+            if (is_cls) {
+                for (int c = 0; c < S; ++c) wm += miss[c];
+            } else {
+                wm = miss[0];
+            }
+        }
         for (int b = 0; b < nbins - 1; ++b) {
             for (int c = 0; c < S; ++c) left[c] += Hj[b * S + c];
             if (is_cls) {
@@ -321,26 +375,39 @@ static __device__ __forceinline__ void tree_split_body(
                 wl = left[0];
             }
             if (extra_mode && b != rand_bin) continue;
-            const float wr = wp - wl;
-            if (COUNTED) {
-                const float cl = left[cnt_stat];
-                const float cr = s_parent[cnt_stat] - cl;
-                if (cl < min_leaf_w || cr < min_leaf_w) continue;
-                if (!(wl > 0.f && wr > 0.f)) continue;
-            } else {
-                if (wl < min_leaf_w || wr < min_leaf_w) continue;
+            float gain;
+            if (split_candidate<COUNTED>(left, wl, s_parent, wp, imp_p, S,
+                                         is_cls, crit, min_leaf_w, cnt_stat,
+                                         &gain)) {
+                // deterministic tie-break: larger gain, then lower
+                // feature/bin
+                if (gain > best_gain + 1e-12f) {
+                    best_gain = gain;
+                    best_feat = j;
+                    best_bin = b;
+                    best_wl = wl;
+                    // no missing weight here: majority side
+                    if (MISSING) best_ml = (!(wm > 0.f) && wl + wl > wp);
+                }
             }
-            const float imp_l = impurity(left, wl, S, is_cls, crit);
-            float right[36];
-            for (int c = 0; c < S; ++c) right[c] = s_parent[c] - left[c];
-            const float imp_r = impurity(right, wr, S, is_cls, crit);
-            const float gain = imp_p - (wl * imp_l + wr * imp_r) / wp;
-            // deterministic tie-break: larger gain, then lower feature/bin
-            if (gain > best_gain + 1e-12f) {
-                best_gain = gain;
-                best_feat = j;
-                best_bin = b;
-                best_wl = wl;
+            if (MISSING && wm > 0.f) {
+                float wlm = 0.f;
+                for (int c = 0; c < S; ++c) lm[c] = left[c] + miss[c];
+                if (is_cls) {
+                    for (int c = 0; c < S; ++c) wlm += lm[c];
+                } else {
+                    wlm = lm[0];
+                }
+                if (split_candidate<COUNTED>(lm, wlm, s_parent, wp, imp_p,
+                                             S, is_cls, crit, min_leaf_w,
+                                             cnt_stat, &gain) &&
+                    gain > best_gain + 1e-12f) {
+                    best_gain = gain;
+                    best_feat = j;
+                    best_bin = b;
+                    best_wl = wlm;
+                    best_ml = 1;
+                }
             }
         }
     }
@@ -353,12 +420,14 @@ static __device__ __forceinline__ void tree_split_body(
         const int of = __shfl_down(best_feat, off);
         const int ob = __shfl_down(best_bin, off);
         const float owl = __shfl_down(best_wl, off);
+        const int oml = MISSING ? __shfl_down(best_ml, off) : 0;
         const bool take = (og > best_gain + 1e-12f) ||
                           (og > best_gain - 1e-12f && of >= 0 &&
                            (best_feat < 0 || of < best_feat ||
                             (of == best_feat && ob < best_bin)));
         if (take) {
             best_gain = og; best_feat = of; best_bin = ob; best_wl = owl;
+            best_ml = oml;
         }
     }
     if (lane == 0) {
@@ -366,6 +435,7 @@ static __device__ __forceinline__ void tree_split_body(
         s_best_feat[wid] = best_feat;
         s_best_bin[wid] = best_bin;
         s_best_wl[wid] = best_wl;
+        if (MISSING) s_best_ml[wid] = best_ml;
     }
     __syncthreads();
     if (tid == 0) {
@@ -383,6 +453,7 @@ static __device__ __forceinline__ void tree_split_body(
                 s_best_feat[0] = of;
                 s_best_bin[0] = s_best_bin[w2];
                 s_best_wl[0] = s_best_wl[w2];
+                if (MISSING) s_best_ml[0] = s_best_ml[w2];
             }
         }
         out_feat[node] = s_best_gain[0] > 0.f ? s_best_feat[0] : -1;
@@ -390,11 +461,14 @@ static __device__ __forceinline__ void tree_split_body(
         out_wl[node] = s_best_wl[0];
         out_gain[node] = s_best_gain[0];
         out_imp[node] = imp_p;
+        if (MISSING)
+            out_mleft[node] = s_best_gain[0] > 0.f ? s_best_ml[0] : 0;
     }
     for (int c = tid; c < S; c += blockDim.x)
         out_stats[(long long)node * S + c] = s_parent[c];
     __syncthreads();
-    // left stats of the winning split (prefix sum over its bins)
+    // left stats of the winning split (prefix sum over its bins, then the
+    // missing bin when it goes left: all zeros there on a majority flag)
     const int wf = (s_best_gain[0] > 0.f) ? s_best_feat[0] : -1;
     for (int c = tid; c < S; c += blockDim.x) {
         float acc = 0.f;
@@ -402,6 +476,7 @@ static __device__ __forceinline__ void tree_split_body(
             const float* Hw = H + (long long)wf * nbins * S;
             const int wb = s_best_bin[0];
             for (int b = 0; b <= wb; ++b) acc += Hw[b * S + c];
+            if (MISSING && s_best_ml[0]) acc += Hw[(nbins - 1) * S + c];
         }
         out_lstats[(long long)node * S + c] = acc;
     }
@@ -414,10 +489,11 @@ extern "C" __global__ __launch_bounds__(256) void k_tree_split(
     int* __restrict__ out_bin, float* __restrict__ out_wl,
     float* __restrict__ out_gain, float* __restrict__ out_imp,
     float* __restrict__ out_stats, float* __restrict__ out_lstats) {
-    tree_split_body<false>(hist, node_seed, f, nbins, S, is_cls, crit,
-                           m_features, extra_mode, min_leaf_w, out_feat,
-                           out_bin, out_wl, out_gain, out_imp, out_stats,
-                           out_lstats, -1);
+    tree_split_body<false, false>(hist, node_seed, f, nbins, S, is_cls,
+                                  crit, m_features, extra_mode, min_leaf_w,
+                                  out_feat, out_bin, out_wl, out_gain,
+                                  out_imp, out_stats, out_lstats, -1,
+                                  nullptr);
 }
 
 // min_leaf_w is a row-count threshold here; cnt_stat in [0, S)
@@ -429,35 +505,85 @@ extern "C" __global__ __launch_bounds__(256) void k_tree_split_w(
     float* __restrict__ out_gain, float* __restrict__ out_imp,
     float* __restrict__ out_stats, float* __restrict__ out_lstats,
     int cnt_stat) {
-    tree_split_body<true>(hist, node_seed, f, nbins, S, is_cls, crit,
-                          m_features, extra_mode, min_leaf_w, out_feat,
-                          out_bin, out_wl, out_gain, out_imp, out_stats,
-                          out_lstats, cnt_stat);
+    tree_split_body<true, false>(hist, node_seed, f, nbins, S, is_cls, crit,
+                                 m_features, extra_mode, min_leaf_w,
+                                 out_feat, out_bin, out_wl, out_gain,
+                                 out_imp, out_stats, out_lstats, cnt_stat,
+                                 nullptr);
+}
+
+// the MISSING instantiations: bin nbins-1 is the missing bin, no ExtraTrees
+extern "C" __global__ __launch_bounds__(256) void k_tree_split_m(
+    const float* __restrict__ hist, const unsigned* __restrict__ node_seed,
+    int f, int nbins, int S, int is_cls, int crit, int m_features,
+    float min_leaf_w, int* __restrict__ out_feat,
+    int* __restrict__ out_bin, float* __restrict__ out_wl,
+    float* __restrict__ out_gain, float* __restrict__ out_imp,
+    float* __restrict__ out_stats, float* __restrict__ out_lstats,
+    int* __restrict__ out_mleft) {
+    tree_split_body<false, true>(hist, node_seed, f, nbins, S, is_cls, crit,
+                                 m_features, 0, min_leaf_w, out_feat,
+                                 out_bin, out_wl, out_gain, out_imp,
+                                 out_stats, out_lstats, -1, out_mleft);
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_tree_split_wm(
+    const float* __restrict__ hist, const unsigned* __restrict__ node_seed,
+    int f, int nbins, int S, int is_cls, int crit, int m_features,
+    float min_leaf_w, int* __restrict__ out_feat,
+    int* __restrict__ out_bin, float* __restrict__ out_wl,
+    float* __restrict__ out_gain, float* __restrict__ out_imp,
+    float* __restrict__ out_stats, float* __restrict__ out_lstats,
+    int cnt_stat, int* __restrict__ out_mleft) {
+    tree_split_body<true, true>(hist, node_seed, f, nbins, S, is_cls, crit,
+                                m_features, 0, min_leaf_w, out_feat,
+                                out_bin, out_wl, out_gain, out_imp,
+                                out_stats, out_lstats, cnt_stat, out_mleft);
 }
 
 // ---------------------------------------------------------------------- //
 // K3: per-chunk left counts (split nodes only)
 // chunks here carry {part_slot, tree_slot, row_start, row_count}
 // ---------------------------------------------------------------------- //
+// The one partition predicate of K3 and K4: a row goes left iff
+// code <= b || (mleft && code == missing_code).  split_mleft is nullable
+// (no slot sends its missing rows left); a slot whose flag is 0 gets the
+// impossible code -1, so the row test stays two compares.
+struct PartSplit {
+    int jf, b, miss;
+    __device__ __forceinline__ PartSplit(const int* split_feat,
+                                         const int* split_bin,
+                                         const int* split_mleft,
+                                         int part_slot, int missing_code)
+        : jf(split_feat[part_slot]), b(split_bin[part_slot]),
+          miss((split_mleft != nullptr && split_mleft[part_slot] != 0)
+                   ? missing_code : -1) {}
+    __device__ __forceinline__ bool left(const unsigned char* codes,
+                                         long long i, int fp) const {
+        const int c = codes[i * fp + jf];
+        return c <= b || c == miss;
+    }
+};
+
 extern "C" __global__ __launch_bounds__(256) void k_part_count(
     const unsigned char* __restrict__ codes, const int* __restrict__ sample_idx,
     const int* __restrict__ chunks, const int* __restrict__ split_feat,
-    const int* __restrict__ split_bin, long long n, int fp,
-    int* __restrict__ out_counts) {
+    const int* __restrict__ split_bin, const int* __restrict__ split_mleft,
+    int missing_code, long long n, int fp, int* __restrict__ out_counts) {
     const int chunk = blockIdx.x;
     const int part_slot = chunks[chunk * 4 + 0];
     const int tree_slot = chunks[chunk * 4 + 1];
     const int row_start = chunks[chunk * 4 + 2];
     const int row_count = chunks[chunk * 4 + 3];
-    const int jf = split_feat[part_slot];
-    const int b = split_bin[part_slot];
+    const PartSplit sp(split_feat, split_bin, split_mleft, part_slot,
+                       missing_code);
     const int* si = sample_idx + (long long)tree_slot * n + row_start;
     __shared__ int s_cnt;
     if (threadIdx.x == 0) s_cnt = 0;
     __syncthreads();
     int cnt = 0;
     for (int r = threadIdx.x; r < row_count; r += blockDim.x)
-        if (codes[(long long)si[r] * fp + jf] <= b) ++cnt;
+        if (sp.left(codes, si[r], fp)) ++cnt;
     atomicAdd(&s_cnt, cnt);
     __syncthreads();
     if (threadIdx.x == 0) out_counts[chunk] = s_cnt;
@@ -472,6 +598,7 @@ extern "C" __global__ __launch_bounds__(256) void k_part_scatter(
     const unsigned char* __restrict__ codes,
     const int* __restrict__ sample_idx_in, const int* __restrict__ chunks,
     const int* __restrict__ split_feat, const int* __restrict__ split_bin,
+    const int* __restrict__ split_mleft, int missing_code,
     const int* __restrict__ left_base, const int* __restrict__ right_base,
     long long n, int fp, int* __restrict__ sample_idx_out) {
     const int chunk = blockIdx.x;
@@ -479,8 +606,8 @@ extern "C" __global__ __launch_bounds__(256) void k_part_scatter(
     const int tree_slot = chunks[chunk * 4 + 1];
     const int row_start = chunks[chunk * 4 + 2];
     const int row_count = chunks[chunk * 4 + 3];
-    const int jf = split_feat[part_slot];
-    const int b = split_bin[part_slot];
+    const PartSplit sp(split_feat, split_bin, split_mleft, part_slot,
+                       missing_code);
     const int* si = sample_idx_in + (long long)tree_slot * n + row_start;
     int* so = sample_idx_out + (long long)tree_slot * n;
 
@@ -499,7 +626,7 @@ extern "C" __global__ __launch_bounds__(256) void k_part_scatter(
         bool p = false;
         if (valid) {
             i = si[r];
-            p = codes[(long long)i * fp + jf] <= b;
+            p = sp.left(codes, i, fp);
         }
         const unsigned long long mask = __ballot(p);
         const int before =
@@ -569,14 +696,35 @@ extern "C" hipError_t skdist_tree_split(
     int nbins, int S, int is_cls, int crit, int m_features, int extra_mode,
     float min_leaf, int cnt_stat, void* out_feat, void* out_bin,
     void* out_wl, void* out_gain, void* out_imp, void* out_stats,
-    void* out_lstats, hipStream_t stream) {
+    void* out_lstats, int missing, void* out_mleft, hipStream_t stream) {
     if (n_frontier <= 0) return hipSuccess;
     if (S <= 0 || S > 32 || cnt_stat >= S) return hipErrorInvalidValue;
+    // the missing scan needs a present bin below the missing one, its own
+    // output, and has no ExtraTrees mode
+    if (missing && (nbins < 2 || out_mleft == nullptr || extra_mode))
+        return hipErrorInvalidValue;
     // per-node parallelism is one thread per feature: size the block to
     // f so low-f datasets don't idle 3/4 of each workgroup
     const int threads = f >= 192 ? 256 : (f >= 96 ? 128 : 64);
-    if (cnt_stat < 0)
-        hipLaunchKernelGGL(k_tree_split, dim3(n_frontier), dim3(threads), 0,
+    const dim3 grid(n_frontier), block(threads);
+    if (missing && cnt_stat < 0)
+        hipLaunchKernelGGL(k_tree_split_m, grid, block, 0, stream,
+                           (const float*)hist, (const unsigned*)node_seed,
+                           f, nbins, S, is_cls, crit, m_features, min_leaf,
+                           (int*)out_feat, (int*)out_bin, (float*)out_wl,
+                           (float*)out_gain, (float*)out_imp,
+                           (float*)out_stats, (float*)out_lstats,
+                           (int*)out_mleft);
+    else if (missing)
+        hipLaunchKernelGGL(k_tree_split_wm, grid, block, 0, stream,
+                           (const float*)hist, (const unsigned*)node_seed,
+                           f, nbins, S, is_cls, crit, m_features, min_leaf,
+                           (int*)out_feat, (int*)out_bin, (float*)out_wl,
+                           (float*)out_gain, (float*)out_imp,
+                           (float*)out_stats, (float*)out_lstats, cnt_stat,
+                           (int*)out_mleft);
+    else if (cnt_stat < 0)
+        hipLaunchKernelGGL(k_tree_split, grid, block, 0,
                            stream, (const float*)hist,
                            (const unsigned*)node_seed, f, nbins, S, is_cls,
                            crit, m_features, extra_mode, min_leaf,
@@ -584,7 +732,7 @@ extern "C" hipError_t skdist_tree_split(
                            (float*)out_gain, (float*)out_imp,
                            (float*)out_stats, (float*)out_lstats);
     else
-        hipLaunchKernelGGL(k_tree_split_w, dim3(n_frontier), dim3(threads),
+        hipLaunchKernelGGL(k_tree_split_w, grid, block,
                            0, stream, (const float*)hist,
                            (const unsigned*)node_seed, f, nbins, S, is_cls,
                            crit, m_features, extra_mode, min_leaf,
@@ -594,27 +742,38 @@ extern "C" hipError_t skdist_tree_split(
     return hipGetLastError();
 }
 
+// split_mleft == nullptr: no slot sends its missing rows left (then
+// missing_code is not read); else missing_code is a uint8 code
 extern "C" hipError_t skdist_part_count(
     const void* codes, const void* sample_idx, const void* chunks,
-    const void* split_feat, const void* split_bin, long long n, int fp,
-    int n_chunks, void* out_counts, hipStream_t stream) {
+    const void* split_feat, const void* split_bin, const void* split_mleft,
+    int missing_code, long long n, int fp, int n_chunks, void* out_counts,
+    hipStream_t stream) {
+    if (n_chunks <= 0) return hipSuccess;
+    if (split_mleft != nullptr && (missing_code < 0 || missing_code > 255))
+        return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_part_count, dim3(n_chunks), dim3(256), 0, stream,
                        (const unsigned char*)codes, (const int*)sample_idx,
                        (const int*)chunks, (const int*)split_feat,
-                       (const int*)split_bin, n, fp, (int*)out_counts);
+                       (const int*)split_bin, (const int*)split_mleft,
+                       missing_code, n, fp, (int*)out_counts);
     return hipGetLastError();
 }
 
 extern "C" hipError_t skdist_part_scatter(
     const void* codes, const void* sample_idx_in, const void* chunks,
-    const void* split_feat, const void* split_bin, const void* left_base,
-    const void* right_base, long long n, int fp, int n_chunks,
-    void* sample_idx_out, hipStream_t stream) {
+    const void* split_feat, const void* split_bin, const void* split_mleft,
+    int missing_code, const void* left_base, const void* right_base,
+    long long n, int fp, int n_chunks, void* sample_idx_out,
+    hipStream_t stream) {
     if (n_chunks <= 0) return hipSuccess;
+    if (split_mleft != nullptr && (missing_code < 0 || missing_code > 255))
+        return hipErrorInvalidValue;
     hipLaunchKernelGGL(k_part_scatter, dim3(n_chunks), dim3(256), 0,
                        stream, (const unsigned char*)codes,
                        (const int*)sample_idx_in, (const int*)chunks,
                        (const int*)split_feat, (const int*)split_bin,
+                       (const int*)split_mleft, missing_code,
                        (const int*)left_base, (const int*)right_base, n,
                        fp, (int*)sample_idx_out);
     return hipGetLastError();

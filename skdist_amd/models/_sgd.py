@@ -16,7 +16,8 @@ Design (MI355X-first):
         (samples with ``fold_id[i] == col_fold[c]`` get gradient 0);
       - ``col_class`` : target class for internal one-vs-rest multiclass
         (binary targets are class 1 of 2);
-      - ``col_lr`` / ``col_l2``: per-column hyper-parameters.
+      - ``col_lr`` / ``col_l2`` / ``col_l1``: per-column hyper-parameters
+        (``col_l1`` optional: L1 / elastic-net, see ``_l1_clip_torch``).
 
   * the same code runs three ways:
       - torch CPU fp32 — the ``sc=None`` path and the numerics reference;
@@ -328,10 +329,16 @@ class ColumnSpec:
     subset — masked rows of W are pinned to 0 after every update, so
     column c trains exactly the model on its feature subset (the batched
     DistFeatureEliminator path; intercept/pad rows must be 1).
+
+    ``col_l1`` (optional, [ncols] >= 0): per-column L1 coefficient.
+    ``None`` or all-zero keeps the L2-only solve (same code path, same
+    kernels); any positive entry routes the whole solve through the
+    cumulative-penalty L1 variants, where columns with ``col_l1 == 0``
+    still compute bit-for-bit what the L2-only solve computes.
     """
 
     def __init__(self, device, col_fold, col_class, col_lr, col_l2,
-                 col_class2=None, feat_mask=None):
+                 col_class2=None, feat_mask=None, col_l1=None):
         as_t = lambda a, dt: torch.as_tensor(
             np.ascontiguousarray(a), dtype=dt, device=device
         )
@@ -346,6 +353,12 @@ class ColumnSpec:
             None if feat_mask is None else as_t(feat_mask, torch.uint8)
         )
         self.ncols = len(col_fold)
+        if col_l1 is not None:
+            l1 = np.ascontiguousarray(col_l1, dtype=np.float32)
+            if l1.shape != (self.ncols,) or not np.all(l1 >= 0.0):
+                raise ValueError("col_l1 must be [ncols] and >= 0")
+            col_l1 = as_t(l1, torch.float32) if l1.any() else None
+        self.col_l1 = col_l1
 
 
 def batched_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
@@ -377,6 +390,11 @@ def batched_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
 
     W = torch.zeros(fa, spec.ncols, dtype=torch.float32, device=device)
     V = torch.zeros_like(W) if momentum > 0.0 else None
+    # L1 credits (u+q, u-q) per weight; None keeps the L2-only step
+    l1_state = (
+        (torch.zeros_like(W), torch.zeros_like(W))
+        if getattr(spec, "col_l1", None) is not None else None
+    )
     rng = np.random.default_rng(seed)
     perm = torch.as_tensor(
         rng.permutation(n), dtype=torch.int64, device=device
@@ -392,20 +410,61 @@ def batched_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
             _sgd_step_torch(
                 ds.Xaug, ds.y_float, ds.fold_id, idx, W, V, spec,
                 loss_id, lr_scale, momentum, ds.intercept_row,
-                row_w=ds.row_w,
+                row_w=ds.row_w, l1_state=l1_state,
             )
             if fmask is not None:
                 W.mul_(fmask)
                 if V is not None:
                     V.mul_(fmask)
+                if l1_state is not None:
+                    l1_state[0].mul_(fmask)
+                    l1_state[1].mul_(fmask)
     return W
 
 
+def _l1_clip_torch(W, cpos, cneg, delta, intercept_row):
+    """Cumulative-penalty L1 step (Tsuruoka, Tsujii & Ananiadou 2009),
+    in place, after the gradient step.
+
+    Per weight the solver tracks ``q``, the signed penalty actually
+    applied so far, against ``u``, the penalty that could have been
+    applied; a weight is clipped towards 0 by what it still owes, never
+    across 0, and a weight at exactly 0 stays there.  The state is held
+    as the two credits ``cpos = u + q`` (owed by a positive weight) and
+    ``cneg = u - q`` (owed by a negative one) instead of ``u`` and ``q``:
+    both stay small while a weight keeps its sign, where ``u + q`` would
+    cancel two numbers that grow with the step count.  ``delta`` [ncols]
+    is this step's advance of ``u``; the intercept row is skipped.
+    k_reduce_update_l1 (ops/csrc/sgd_kernels.hip) is the same arithmetic.
+    """
+    cpos.add_(delta.unsqueeze(0))
+    cneg.add_(delta.unsqueeze(0))
+    zero = torch.zeros_like(W)
+    Wn = torch.where(
+        W > 0, torch.maximum(W - cpos, zero),
+        torch.where(W < 0, torch.minimum(W + cneg, zero), W))
+    Wn[intercept_row] = W[intercept_row]
+    d = Wn - W
+    cpos.add_(d)
+    cneg.sub_(d)
+    cpos[intercept_row] = 0.0
+    cneg[intercept_row] = 0.0
+    W.copy_(Wn)
+
+
 def _sgd_step_torch(Xaug, y_float, fold_id, idx, W, V, spec, loss_id,
-                    lr_scale, momentum, intercept_row=None, row_w=None):
+                    lr_scale, momentum, intercept_row=None, row_w=None,
+                    l1_state=None):
     """One mini-batch step, eager torch — the numerics reference the HIP
     kernels are tested against (fp32 on CPU; on GPU it mirrors the kernel's
-    bf16-in/fp32-accumulate)."""
+    bf16-in/fp32-accumulate).
+
+    ``l1_state`` = (cpos, cneg) turns on the L1 step for the columns with
+    ``spec.col_l1 > 0``.  The threshold advances by
+    ``lr * lr_scale * l1 / (1 - momentum)`` per step: the L2 term rides
+    inside the momentum buffer, which amplifies it by 1/(1 - momentum) in
+    the long run; a threshold applied outside the buffer is not amplified,
+    so it carries the factor itself to keep l1 and l2 on one scale."""
     Xb = Xaug[idx]                       # [m, f+1]
     m = Xb.shape[0]
     comp = Xb.dtype
@@ -454,6 +513,10 @@ def _sgd_step_torch(Xaug, y_float, fold_id, idx, W, V, spec, loss_id,
         W.sub_(V)
     else:
         W.sub_(step)
+    if l1_state is not None:
+        delta = (spec.col_lr * lr_scale * spec.col_l1
+                 * (1.0 / (1.0 - momentum)))
+        _l1_clip_torch(W, l1_state[0], l1_state[1], delta, ir)
 
 
 # --------------------------------------------------------------------- #

@@ -20,7 +20,10 @@ CSR and trains the same column batch with gather/scatter kernels
     dense path's contract) lets one lane own (feature, column): no
     atomics, deterministic;
   * L2 decay of all f rows is applied lazily as a per-column scale
-    (exactly the dense update's math; see the kernel header).
+    (exactly the dense update's math; see the kernel header);
+  * an L1 penalty (``ColumnSpec.col_l1``) is applied lazily too: the
+    cumulative-penalty rule, caught up per weight whenever a batch
+    touches its feature and once more at the end of the fit.
 
 Solver deltas vs the dense path, by design: no standardization (hashed
 text is already unit-scale; centering would densify) and no momentum
@@ -274,7 +277,20 @@ def sparse_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
     step per (feature, column) — rare text features take full-size
     first steps instead of 1/batch-size ones.  The lazy L2 decay is
     unaffected.  ``adaptive=False`` runs the dense solver's plain-SGD
-    update (the dense-equivalence mode the tests use)."""
+    update (the dense-equivalence mode the tests use).
+
+    ``spec.col_l1`` (some column with l1 > 0) adds the cumulative-penalty
+    L1 update, applied lazily like the L2 decay (kernel header:
+    ``sparse_sgd_kernels.hip``; eager twin: ``_sp_l1_touch``).  Under
+    ``adaptive`` the L1 threshold of a weight accrues at that weight's
+    Adagrad rate, so pure L1 tracks a proximal solver's support; the L2
+    part keeps its rate-free lazy scale, so elastic-net under
+    ``adaptive=True`` follows sklearn less closely than pure L1 does.
+    Memory: the L1 state is allocated only in this mode, one fp32 table
+    of f x ncols_pad (``q``) and with ``adaptive`` two more (``u``,
+    ``Ulast``) — 4 GiB per table at 2^20 features x 1024 columns, on top
+    of the same-sized W and Adagrad H.  L1 fits run one call per epoch
+    (no hipGraph replay); L2-only fits are untouched."""
     if momentum > 0.0:
         warnings.warn(
             "sparse batched solve runs momentum-free SGD (a momentum "
@@ -302,6 +318,17 @@ def sparse_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
     else:
         H = torch.empty(0, dtype=torch.float32, device=dev)
         Hb = torch.empty(0, dtype=torch.float32, device=dev)
+    l1 = None
+    if getattr(spec, "col_l1", None) is not None:
+        none = torch.empty(0, dtype=torch.float32, device=dev)
+        l1 = {
+            "col": torch.zeros(cp, dtype=torch.float32, device=dev),
+            "U": torch.zeros(cp, dtype=torch.float32, device=dev),
+            "q": torch.zeros(ds.f, cp, dtype=torch.float32, device=dev),
+            "u": torch.zeros_like(H) if adaptive else none,
+            "ul": torch.zeros_like(H) if adaptive else none,
+        }
+        l1["col"][:ncols] = spec.col_l1
 
     hip = (not force_eager) and _use_hip(dev)
     if hip:
@@ -342,7 +369,31 @@ def sparse_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
                 renorm_free = (
                     epochs * n_batches * np.log(fmin) > np.log(2e-3)
                 )
-        if renorm_free:
+        if l1 is not None:
+            for epoch in range(epochs):
+                lr_scale = 1.0 / (1.0 + lr_decay * epoch)
+                ext.sp_sgd_epoch_l1(
+                    sh["crow"], sh["cidx"], sh["cval"], W[: ds.f], Wb, s,
+                    H, Hb, G, part, sh["y"], sh["fold"], rw,
+                    col["cls"], col["fold"], col["cls2"], col["lr"],
+                    col["l2"], sh["ufeat"], sh["cptr"], sh["ridx"],
+                    sh["bval"], sh["ub_ptr"], sh["inv_m"],
+                    int(batch_size), int(loss_id), float(lr_scale),
+                    l1["col"], l1["U"], l1["q"], l1["u"], l1["ul"])
+                f = (np.float32(1.0)
+                     - (lr_pad * np.float32(lr_scale)) * l2_pad)
+                for _ in range(n_batches):
+                    s_host *= f
+                if float(s_host.min()) < 1e-3:
+                    # every stored-unit L1 quantity changes units with W
+                    ext.sp_renorm_l1(W[: ds.f], s, l1["q"], l1["u"],
+                                     l1["ul"])
+                    l1["U"].mul_(s)
+                    s.fill_(1.0)
+                    s_host[:] = 1.0
+            ext.sp_l1_flush(W[: ds.f], H, l1["U"], l1["q"], l1["u"],
+                            l1["ul"])
+        elif renorm_free:
             ext.sp_sgd_solve(
                 sh["crow"], sh["cidx"], sh["cval"], W[: ds.f], Wb, s,
                 H, Hb, G, part, sh["y"], sh["fold"], rw,
@@ -370,7 +421,7 @@ def sparse_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
                     s_host[:] = 1.0
     else:
         _sparse_sgd_eager(ds, sh, W, Wb, s, H, Hb, col, loss_id, epochs,
-                          batch_size, lr_decay, cp)
+                          batch_size, lr_decay, cp, l1=l1)
 
     W[: ds.f].mul_(s.unsqueeze(0))
     W[ds.f] = Wb
@@ -392,11 +443,51 @@ def _padded_cols(spec, cp, dev):
     }
 
 
+def _sp_l1_touch(Wt, H, l1, rows):
+    """Eager twin of the kernels' ``sp_l1_touch`` on the weight rows
+    ``rows`` (None = all): bring each weight's L1 credit ``u`` up to its
+    column's ``U``, clip the weight towards 0 by what it still owes
+    (``u + q`` for a positive weight, ``u - q`` for a negative one; a
+    zero stays zero) and book the applied penalty in ``q``.  With the
+    Adagrad accumulator H the credit accrues at the weight's own rate,
+    and nothing accrues while H is 0."""
+    sel = (lambda t: t) if rows is None else (
+        lambda t: t.index_select(0, rows))
+    U = l1["U"].unsqueeze(0)
+    w = sel(Wt)
+    q = sel(l1["q"])
+    if H.numel():
+        h = sel(H)
+        u = sel(l1["u"])
+        u = torch.where(
+            h > 0, u + (U - sel(l1["ul"])) * torch.rsqrt(h + 1e-12), u)
+        ul = U.expand_as(u)
+    else:
+        u = U.expand_as(w)
+    zero = torch.zeros_like(w)
+    wn = torch.where(
+        w > 0, torch.maximum(w - (u + q), zero),
+        torch.where(w < 0, torch.minimum(w + (u - q), zero), w))
+    q = q + (wn - w)
+    if rows is None:
+        Wt.copy_(wn)
+        l1["q"].copy_(q)
+        if H.numel():
+            l1["u"].copy_(u)
+            l1["ul"].copy_(ul)
+    else:
+        Wt.index_copy_(0, rows, wn)
+        l1["q"].index_copy_(0, rows, q)
+        if H.numel():
+            l1["u"].index_copy_(0, rows, u)
+            l1["ul"].index_copy_(0, rows, ul.contiguous())
+
+
 def _sparse_sgd_eager(ds, sh, W, Wb, s, H, Hb, col, loss_id, epochs,
-                      batch_size, lr_decay, cp):
+                      batch_size, lr_decay, cp, l1=None):
     """Eager torch mirror of the kernels' number flow (fp32 math, bf16
-    G round-trip, lazy L2 scale).  The numerics reference for the GPU
-    tests; also the CPU execution path."""
+    G round-trip, lazy L2 scale, lazy L1 touches).  The numerics
+    reference for the GPU tests; also the CPU execution path."""
     dev = ds.device
     n, f = ds.n, ds.f
     crow, cidx, cval = sh["crow"], sh["cidx"], sh["cval"]
@@ -417,6 +508,12 @@ def _sparse_sgd_eager(ds, sh, W, Wb, s, H, Hb, col, loss_id, epochs,
                     crow[start + 1: start + m + 1]
                     - crow[start: start + m])
             )
+            if l1 is not None:
+                # the batch's features, touched before the forward and
+                # again after their gradient step (k_sp_l1_catchup /
+                # k_sp_update_l1)
+                uf = torch.unique(jj)
+                _sp_l1_touch(Wt, H, l1, uf)
             contrib = vv.unsqueeze(1) * Wt.index_select(0, jj)
             Z = torch.zeros(m, cp, dtype=torch.float32, device=dev)
             Z.index_add_(0, rl, contrib)
@@ -458,6 +555,8 @@ def _sparse_sgd_eager(ds, sh, W, Wb, s, H, Hb, col, loss_id, epochs,
             else:
                 Wb.sub_(lr * gb)
             s.mul_(1.0 - lr * col["l2"])
+            if l1 is not None:
+                l1["U"].add_(lr * l1["col"] / s)
             GW = torch.zeros_like(Wt)
             GW.index_add_(0, jj, vv.unsqueeze(1) * G.index_select(0, rl))
             GW.mul_(im)
@@ -467,10 +566,19 @@ def _sparse_sgd_eager(ds, sh, W, Wb, s, H, Hb, col, loss_id, epochs,
                         / s.unsqueeze(0))
             else:
                 Wt.sub_(lr.unsqueeze(0) * GW / s.unsqueeze(0))
+            if l1 is not None:
+                _sp_l1_touch(Wt, H, l1, uf)
         # renorm check per epoch, matching the HIP driver
         if float(s.min()) < 1e-3:
             Wt.mul_(s.unsqueeze(0))
+            if l1 is not None:
+                for k in ("q", "u", "ul"):
+                    if l1[k].numel():
+                        l1[k].mul_(s.unsqueeze(0))
+                l1["U"].mul_(s)
             s.fill_(1.0)
+    if l1 is not None:
+        _sp_l1_touch(Wt, H, l1, None)  # end-of-fit flush (k_sp_l1_flush)
 
 
 # --------------------------------------------------------------------- #

@@ -123,14 +123,20 @@ class _BatchedLinearBase(BaseEstimator):
         return _DatasetPrefetch(build)
 
     def _lam(self, n_train):
-        """Per-column L2 coefficient from the sklearn-style hyper-param."""
-        C = getattr(self, "C", None)
-        if C is not None:
-            return 1.0 / (float(C) * max(n_train, 1))
-        return float(getattr(self, "alpha", 1.0)) / max(n_train, 1)
+        """Per-column (l2, l1) coefficients from the sklearn-style
+        hyper-params (see ``_lam_from``)."""
+        return _lam_from(
+            {"C": getattr(self, "C", None),
+             "alpha": getattr(self, "alpha", 1.0),
+             # estimators pickled before the penalty parameters existed
+             "penalty": getattr(self, "penalty", "l2"),
+             "l1_ratio": getattr(self, "l1_ratio", None)},
+            n_train)
 
     def _hyper_names(self):
-        return {"C"} if hasattr(self, "C") else {"alpha"}
+        if hasattr(self, "C"):
+            return {"C", "penalty", "l1_ratio"}
+        return {"alpha"}
 
     # ------------------------------------------------------------------ #
     def _merged_sample_weight(self, y, sample_weight):
@@ -176,13 +182,14 @@ class _BatchedLinearBase(BaseEstimator):
         else:
             ncols = 1
             col_class = np.array([-1], dtype=np.int32)
-        lam = self._lam(ds.n)
+        l2, l1 = self._lam(ds.n)
         spec = ColumnSpec(
             ds.device,
             col_fold=np.full(ncols, -2, dtype=np.int32),
             col_class=col_class,
             col_lr=np.full(ncols, self.lr, dtype=np.float32),
-            col_l2=np.full(ncols, lam, dtype=np.float32),
+            col_l2=np.full(ncols, l2, dtype=np.float32),
+            col_l1=np.full(ncols, l1, dtype=np.float32),
         )
         W = batched_sgd_fit(
             ds, spec, self._loss, self.epochs, self.batch_size,
@@ -345,6 +352,7 @@ class _BatchedLinearBase(BaseEstimator):
             else list(range(n_cand))
         )
         col_fold, col_class, col_lr, col_l2, col_model = [], [], [], [], []
+        col_l1 = []
         model_folds = []   # per model: its test fold, -2 for full-data
         local_tasks = []   # (task_id, model_idx, fold)
         full_models = {}   # cand_id -> model_idx of the full-data model
@@ -355,12 +363,13 @@ class _BatchedLinearBase(BaseEstimator):
             lr = float(params.get("lr", self.lr))
             merged = {**self_params, **params}
             for fold in range(n_folds):
-                lam = _lam_from(merged, fold_train_n[fold])
+                l2, l1 = _lam_from(merged, fold_train_n[fold])
                 for cc in cls:
                     col_fold.append(fold)
                     col_class.append(cc)
                     col_lr.append(lr)
-                    col_l2.append(lam)
+                    col_l2.append(l2)
+                    col_l1.append(l1)
                     col_model.append(model_idx)
                 model_folds.append(fold)
                 local_tasks.append((ci * n_folds + fold, model_idx, fold))
@@ -369,12 +378,13 @@ class _BatchedLinearBase(BaseEstimator):
             # fold models so the search's "refit" is a column extraction
             # instead of a second solve (MI355X-batched replacement for
             # reference search.py:543-550's driver-side refit)
-            lam = _lam_from(merged, ds.n)
+            l2, l1 = _lam_from(merged, ds.n)
             for cc in cls:
                 col_fold.append(-2)  # trains on every row
                 col_class.append(cc)
                 col_lr.append(lr)
-                col_l2.append(lam)
+                col_l2.append(l2)
+                col_l1.append(l1)
                 col_model.append(model_idx)
             model_folds.append(-2)
             full_models[ci] = model_idx
@@ -389,6 +399,7 @@ class _BatchedLinearBase(BaseEstimator):
                 col_class=np.asarray(col_class, dtype=np.int32),
                 col_lr=np.asarray(col_lr, dtype=np.float32),
                 col_l2=np.asarray(col_l2, dtype=np.float32),
+                col_l1=np.asarray(col_l1, dtype=np.float32),
             )
             W = batched_sgd_fit(
                 ds, spec, self._loss, self.epochs, self.batch_size,
@@ -509,7 +520,7 @@ class _BatchedLinearBase(BaseEstimator):
             else list(range(n_sets))
         )
         fold_train_n = [len(tr) for tr, _ in cv_splits]
-        col_fold, col_class, col_lr, col_l2 = [], [], [], []
+        col_fold, col_class, col_lr, col_l2, col_l1 = [], [], [], [], []
         model_folds = []
         masks = []          # per MODEL (shared by its cpm columns)
         local_rows = []     # (set_id, model_idx, fold | -2)
@@ -522,12 +533,13 @@ class _BatchedLinearBase(BaseEstimator):
                 n_train = (
                     fold_train_n[fold] if fold >= 0 else ds.n
                 )
-                lam = self._lam(n_train)
+                l2, l1 = self._lam(n_train)
                 for cc in cls:
                     col_fold.append(fold)
                     col_class.append(cc)
                     col_lr.append(self.lr)
-                    col_l2.append(lam)
+                    col_l2.append(l2)
+                    col_l1.append(l1)
                 masks.append(m)
                 model_folds.append(fold)
                 local_rows.append((si, model_idx, fold))
@@ -546,6 +558,7 @@ class _BatchedLinearBase(BaseEstimator):
                 col_lr=np.asarray(col_lr, dtype=np.float32),
                 col_l2=np.asarray(col_l2, dtype=np.float32),
                 feat_mask=feat_mask,
+                col_l1=np.asarray(col_l1, dtype=np.float32),
             )
             W = batched_sgd_fit(
                 ds, spec, self._loss, self.epochs, self.batch_size,
@@ -636,14 +649,16 @@ class _BatchedLinearBase(BaseEstimator):
             else list(range(len(problems)))
         )
         counts = np.bincount(ds.y_int.cpu().numpy(), minlength=k)
-        col_class, col_class2, col_lr, col_l2 = [], [], [], []
+        col_class, col_class2, col_lr, col_l2, col_l1 = [], [], [], [], []
         for pi in ids:
             tgt, other = problems[pi]
             n_train = ds.n if other < 0 else counts[tgt] + counts[other]
             col_class.append(tgt)
             col_class2.append(other)
             col_lr.append(self.lr)
-            col_l2.append(self._lam(n_train))
+            l2, l1 = self._lam(n_train)
+            col_l2.append(l2)
+            col_l1.append(l1)
         local = {}
         if ids:
             spec = ColumnSpec(
@@ -653,6 +668,7 @@ class _BatchedLinearBase(BaseEstimator):
                 col_lr=np.asarray(col_lr, dtype=np.float32),
                 col_l2=np.asarray(col_l2, dtype=np.float32),
                 col_class2=np.asarray(col_class2, dtype=np.int32),
+                col_l1=np.asarray(col_l1, dtype=np.float32),
             )
             W = batched_sgd_fit(
                 ds, spec, self._loss, self.epochs, self.batch_size,
@@ -807,10 +823,40 @@ class _BatchedLinearBase(BaseEstimator):
         return metric
 
 
+_PENALTIES = ("l2", "l1", "elasticnet")
+
+
+def _l1_share(params):
+    """rho in [0, 1]: the L1 share of the penalty (sklearn's
+    ``l1_ratio``); validates ``penalty`` / ``l1_ratio``."""
+    penalty = params.get("penalty", "l2")
+    if penalty not in _PENALTIES:   # None too: there is no unpenalised fit
+        raise ValueError(
+            f"penalty must be one of {_PENALTIES}, got {penalty!r}")
+    if penalty == "l2":
+        return 0.0
+    if penalty == "l1":
+        return 1.0
+    rho = params.get("l1_ratio")
+    if (rho is None or isinstance(rho, (bool, str))
+            or not isinstance(rho, (int, float, np.integer, np.floating))
+            or not 0.0 <= float(rho) <= 1.0):
+        raise ValueError(
+            "l1_ratio must be a number in [0, 1] when "
+            f"penalty='elasticnet', got {rho!r}")
+    return float(rho)
+
+
 def _lam_from(params, n_train):
+    """(l2, l1) penalty coefficients of one column, sklearn's
+    parametrisation: lam = 1/(C n_train), l2 = (1-rho) lam, l1 = rho lam
+    (rho = 0 for 'l2', 1 for 'l1', l1_ratio for 'elasticnet').  The
+    ``alpha`` family (Ridge) is L2-only."""
     if "C" in params and params.get("C") is not None:
-        return 1.0 / (float(params["C"]) * max(n_train, 1))
-    return float(params.get("alpha", 1.0)) / max(n_train, 1)
+        lam = 1.0 / (float(params["C"]) * max(n_train, 1))
+        rho = _l1_share(params)
+        return (1.0 - rho) * lam, rho * lam
+    return float(params.get("alpha", 1.0)) / max(n_train, 1), 0.0
 
 
 def sk_clone_without_sc(est):
@@ -840,6 +886,14 @@ class LogisticRegression(ClassifierMixin, _BatchedLinearBase):
     (centering would densify; hashed text is already unit-scale), runs
     momentum-free, and Adagrad-normalizes the data-gradient steps
     unless ``adaptive=False``.
+
+    ``penalty`` is ``"l2"`` (default), ``"l1"`` or ``"elasticnet"`` with
+    ``l1_ratio`` in [0, 1], in sklearn's parametrisation:
+    ``lam = 1 / (C n)``, L2 coefficient ``(1 - l1_ratio) lam``, L1
+    coefficient ``l1_ratio lam``.  The L1 part is the cumulative-penalty
+    update (``_sgd._l1_clip_torch``); it is applied in the solver's
+    standardized space and yields exact ``0.0`` entries in ``coef_``.
+    ``C``, ``penalty`` and ``l1_ratio`` all batch into one search solve.
     """
 
     _loss = LOSS_LOG
@@ -847,8 +901,10 @@ class LogisticRegression(ClassifierMixin, _BatchedLinearBase):
     def __init__(self, C=1.0, lr=0.5, epochs=20, batch_size=8192,
                  momentum=0.9, lr_decay=0.0, standardize=True,
                  class_weight=None, random_state=None, adaptive=None,
-                 sc=None):
+                 sc=None, penalty="l2", l1_ratio=None):
         self.C = C
+        self.penalty = penalty
+        self.l1_ratio = l1_ratio
         self.adaptive = adaptive
         self.class_weight = class_weight
         self.lr_decay = lr_decay
@@ -880,15 +936,18 @@ class LogisticRegression(ClassifierMixin, _BatchedLinearBase):
 
 
 class LinearSVC(ClassifierMixin, _BatchedLinearBase):
-    """Batched-SGD linear SVM (hinge loss, internal one-vs-rest)."""
+    """Batched-SGD linear SVM (hinge loss, internal one-vs-rest).
+    ``penalty`` / ``l1_ratio`` as in :class:`LogisticRegression`."""
 
     _loss = LOSS_HINGE
 
     def __init__(self, C=1.0, lr=0.5, epochs=20, batch_size=8192,
                  momentum=0.9, lr_decay=0.0, standardize=True,
                  class_weight=None, random_state=None, adaptive=None,
-                 sc=None):
+                 sc=None, penalty="l2", l1_ratio=None):
         self.C = C
+        self.penalty = penalty
+        self.l1_ratio = l1_ratio
         self.adaptive = adaptive
         self.class_weight = class_weight
         self.lr_decay = lr_decay

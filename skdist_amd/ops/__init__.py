@@ -181,6 +181,11 @@ def hip_sgd_solve(ds, spec, loss_id, epochs, batch_size, seed, momentum,
     Walks the same per-epoch host-RNG permutations as the torch reference
     (minibatch = slab of the epoch-shuffled copy), so the two paths are
     comparable to bf16 tolerance.  Returns W [fa, ncols] fp32.
+
+    ``spec.col_l1`` set (some column with l1 > 0) switches K3 to
+    k_reduce_update_l1 through the ``*_l1`` entries; it costs two more
+    [fa, ncols_pad] fp32 tables (the per-weight L1 credits).  Without it
+    the calls below are the L2-only ones, unchanged.
     """
     import numpy as np
 
@@ -234,7 +239,31 @@ def hip_sgd_solve(ds, spec, loss_id, epochs, batch_size, seed, momentum,
         ]
         inv_m = torch.tensor(
             [1.0 / max(v, 1e-30) for v in sums], dtype=torch.float32)
-    if lr_decay == 0.0:
+    col_l1 = getattr(spec, "col_l1", None)
+    if col_l1 is not None:
+        if not 0.0 <= momentum < 1.0:
+            raise ValueError("the L1 update needs momentum in [0, 1)")
+        l1_p = _pad_cols(col_l1, ncp, 0.0)
+        cpos = torch.zeros_like(W)
+        cneg = torch.zeros_like(W)
+        if lr_decay == 0.0:
+            ext.sgd_solve_l1(
+                Xs, XsT, GT, W, V, WbfT, partial, ys, folds,
+                cls_p, cfold_p, cls2_p, lr_p, l2_p, fmask, rw_t, inv_m,
+                bs, int(loss_id), float(momentum), int(ds.intercept_row),
+                int(epochs), l1_p, cpos, cneg,
+            )
+        else:
+            for epoch in range(epochs):
+                lr_scale = 1.0 / (1.0 + lr_decay * epoch)
+                ext.sgd_epoch_l1(
+                    Xs, XsT, GT, W, V, WbfT, partial, ys, folds,
+                    cls_p, cfold_p, cls2_p, lr_p, l2_p, fmask, rw_t,
+                    inv_m, bs, int(loss_id), float(lr_scale),
+                    float(momentum), int(ds.intercept_row),
+                    l1_p, cpos, cneg,
+                )
+    elif lr_decay == 0.0:
         # constant lr_scale: every epoch launches the identical
         # sequence — one C++ call, epochs 2..N replay a hipGraph
         ext.sgd_solve(

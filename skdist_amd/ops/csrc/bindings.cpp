@@ -21,6 +21,20 @@ extern "C" hipError_t skdist_sgd_step(
     int gt_stride, int splitk, int loss_id,
     float lr_scale, float momentum, int intercept_row,
     hipStream_t stream);
+// same step with the cumulative-penalty L1 update (k_reduce_update_l1)
+extern "C" hipError_t skdist_sgd_step_l1(
+    const void* Xs, const void* XsT, const void* WbfT_in,
+    void* GT, void* W, void* V, void* WbfT, void* partial,
+    const void* y, const void* fold,
+    const void* col_class, const void* col_fold, const void* col_class2,
+    const void* col_lr, const void* col_l2, const void* fmask,
+    const void* row_w, float inv_m,
+    long long start, long long m, long long n, long long n_pad,
+    long long fa_store, int fa, int ncols_pad,
+    int gt_stride, int splitk, int loss_id,
+    float lr_scale, float momentum, int intercept_row,
+    const void* col_l1, void* cpos, void* cneg,
+    hipStream_t stream);
 
 namespace {
 
@@ -145,6 +159,87 @@ static void run_epochs_graphed(int64_t epochs, hipStream_t torch_stream,
     hipStreamDestroy(s2);
 }
 
+// L1 state of one dense solve: per-column coefficient plus the two
+// per-weight credit tables, all-or-nothing
+struct L1Args {
+    const void* col_l1 = nullptr;
+    void* cpos = nullptr;
+    void* cneg = nullptr;
+};
+
+L1Args check_l1(torch::Tensor& col_l1, torch::Tensor& cpos,
+                torch::Tensor& cneg, torch::Tensor& W, double momentum) {
+    for (auto* t : {&col_l1, &cpos, &cneg}) {
+        CHECK_DEV(*t);
+        CHECK_CONT(*t);
+        TORCH_CHECK(t->scalar_type() == torch::kFloat32, "L1 state is f32");
+    }
+    TORCH_CHECK(col_l1.numel() == W.size(1), "col_l1 must be [ncols_pad]");
+    TORCH_CHECK(cpos.sizes() == W.sizes() && cneg.sizes() == W.sizes(),
+                "L1 credit tables must match W");
+    TORCH_CHECK(momentum >= 0.0 && momentum < 1.0,
+                "momentum must be in [0, 1)");
+    L1Args l1;
+    l1.col_l1 = col_l1.data_ptr();
+    l1.cpos = cpos.data_ptr();
+    l1.cneg = cneg.data_ptr();
+    return l1;
+}
+
+// every mini-batch step of one epoch on `st`; `l1.col_l1 == nullptr`
+// launches the L2-only step
+void enqueue_epoch(const StepArgs& a, torch::Tensor& Xs, torch::Tensor& XsT,
+                   torch::Tensor& GT, torch::Tensor& W, torch::Tensor& V,
+                   torch::Tensor& WbfT, torch::Tensor& partial,
+                   torch::Tensor& y, torch::Tensor& fold,
+                   torch::Tensor& col_class, torch::Tensor& col_fold,
+                   torch::Tensor& col_class2, torch::Tensor& col_lr,
+                   torch::Tensor& col_l2, torch::Tensor& fmask,
+                   torch::Tensor& row_w, const float* inv_p,
+                   int64_t batch_size, int64_t loss_id, float lr_scale,
+                   double momentum, int64_t intercept_row,
+                   const L1Args& l1, hipStream_t st, const char* who) {
+    const bool has_V = V.numel() > 0;
+    int64_t bi = 0;
+    for (int64_t start = 0; start < a.n; start += batch_size, ++bi) {
+        const int64_t m = std::min(batch_size, a.n - start);
+        void* Vp = has_V ? V.data_ptr() : nullptr;
+        const void* fm = fmask.numel() ? fmask.data_ptr() : nullptr;
+        const void* rw = row_w.numel() ? row_w.data_ptr() : nullptr;
+        hipError_t err;
+        if (l1.col_l1 == nullptr) {
+            err = skdist_sgd_step(
+                Xs.data_ptr(), XsT.data_ptr(), WbfT.data_ptr(),
+                GT.data_ptr(), W.data_ptr(), Vp, WbfT.data_ptr(),
+                partial.data_ptr(), y.data_ptr(), fold.data_ptr(),
+                col_class.data_ptr(), col_fold.data_ptr(),
+                col_class2.data_ptr(), col_lr.data_ptr(),
+                col_l2.data_ptr(), fm, rw, inv_p[bi],
+                start, m, a.n, a.n_pad, a.fa_store,
+                (int)a.fa, (int)a.ncols_pad, (int)a.gt_stride,
+                (int)a.splitk, (int)loss_id, lr_scale, (float)momentum,
+                (int)intercept_row, st);
+        } else {
+            err = skdist_sgd_step_l1(
+                Xs.data_ptr(), XsT.data_ptr(), WbfT.data_ptr(),
+                GT.data_ptr(), W.data_ptr(), Vp, WbfT.data_ptr(),
+                partial.data_ptr(), y.data_ptr(), fold.data_ptr(),
+                col_class.data_ptr(), col_fold.data_ptr(),
+                col_class2.data_ptr(), col_lr.data_ptr(),
+                col_l2.data_ptr(), fm, rw, inv_p[bi],
+                start, m, a.n, a.n_pad, a.fa_store,
+                (int)a.fa, (int)a.ncols_pad, (int)a.gt_stride,
+                (int)a.splitk, (int)loss_id, lr_scale, (float)momentum,
+                (int)intercept_row, l1.col_l1, l1.cpos, l1.cneg, st);
+        }
+        TORCH_CHECK(err == hipSuccess, who, ": ", hipGetErrorString(err));
+    }
+}
+
+int64_t n_batches_of(const StepArgs& a, int64_t batch_size) {
+    return (a.n + batch_size - 1) / batch_size;
+}
+
 // one whole epoch: the minibatch loop runs in C++ so the hot path costs
 // one pybind crossing per epoch instead of one per step
 void sgd_epoch(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
@@ -159,27 +254,12 @@ void sgd_epoch(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                double momentum, int64_t intercept_row) {
     auto a = check_args(Xs, XsT, GT, W, partial, y);
     TORCH_CHECK(batch_size % 128 == 0, "batch_size must be a mult of 128");
-    const bool has_V = V.numel() > 0;
     TORCH_CHECK(!inv_m_cpu.is_cuda(), "inv_m must be a CPU tensor");
-    const float* inv_p = (const float*)inv_m_cpu.data_ptr();
-    auto stream = c10::hip::getCurrentHIPStream().stream();
-    int64_t bi = 0;
-    for (int64_t start = 0; start < a.n; start += batch_size, ++bi) {
-        const int64_t m = std::min(batch_size, a.n - start);
-        hipError_t err = skdist_sgd_step(
-            Xs.data_ptr(), XsT.data_ptr(), WbfT.data_ptr(), GT.data_ptr(),
-            W.data_ptr(), has_V ? V.data_ptr() : nullptr, WbfT.data_ptr(),
-            partial.data_ptr(), y.data_ptr(), fold.data_ptr(),
-            col_class.data_ptr(), col_fold.data_ptr(),
-            col_class2.data_ptr(), col_lr.data_ptr(), col_l2.data_ptr(),
-            fmask.numel() ? fmask.data_ptr() : nullptr,
-            row_w.numel() ? row_w.data_ptr() : nullptr, inv_p[bi],
-            start, m, a.n, a.n_pad, a.fa_store,
-            (int)a.fa, (int)a.ncols_pad, (int)a.gt_stride, (int)a.splitk,
-            (int)loss_id, (float)lr_scale, (float)momentum,
-            (int)intercept_row, stream);
-        TORCH_CHECK(err == hipSuccess, "sgd_epoch: ", hipGetErrorString(err));
-    }
+    enqueue_epoch(a, Xs, XsT, GT, W, V, WbfT, partial, y, fold, col_class,
+                  col_fold, col_class2, col_lr, col_l2, fmask, row_w,
+                  (const float*)inv_m_cpu.data_ptr(), batch_size, loss_id,
+                  (float)lr_scale, momentum, intercept_row, L1Args{},
+                  c10::hip::getCurrentHIPStream().stream(), "sgd_epoch");
 }
 
 // all epochs in one call; lr_scale is constant (lr_decay=0), so every
@@ -196,30 +276,68 @@ void sgd_solve(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                int64_t epochs) {
     auto a = check_args(Xs, XsT, GT, W, partial, y);
     TORCH_CHECK(batch_size % 128 == 0, "batch_size must be a mult of 128");
-    const bool has_V = V.numel() > 0;
     const float* inv_p = (const float*)inv_m_cpu.data_ptr();
     auto torch_stream = c10::hip::getCurrentHIPStream().stream();
     auto body = [&](hipStream_t st) {
-        int64_t bi = 0;
-        for (int64_t start = 0; start < a.n; start += batch_size, ++bi) {
-            const int64_t m = std::min(batch_size, a.n - start);
-            hipError_t err = skdist_sgd_step(
-                Xs.data_ptr(), XsT.data_ptr(), WbfT.data_ptr(),
-                GT.data_ptr(), W.data_ptr(),
-                has_V ? V.data_ptr() : nullptr, WbfT.data_ptr(),
-                partial.data_ptr(), y.data_ptr(), fold.data_ptr(),
-                col_class.data_ptr(), col_fold.data_ptr(),
-                col_class2.data_ptr(), col_lr.data_ptr(),
-                col_l2.data_ptr(),
-                fmask.numel() ? fmask.data_ptr() : nullptr,
-                row_w.numel() ? row_w.data_ptr() : nullptr, inv_p[bi],
-                start, m, a.n, a.n_pad, a.fa_store,
-                (int)a.fa, (int)a.ncols_pad, (int)a.gt_stride,
-                (int)a.splitk, (int)loss_id, 1.0f, (float)momentum,
-                (int)intercept_row, st);
-            TORCH_CHECK(err == hipSuccess, "sgd_solve: ",
-                        hipGetErrorString(err));
-        }
+        enqueue_epoch(a, Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+                      col_class, col_fold, col_class2, col_lr, col_l2,
+                      fmask, row_w, inv_p, batch_size, loss_id, 1.0f,
+                      momentum, intercept_row, L1Args{}, st, "sgd_solve");
+    };
+    run_epochs_graphed(epochs, torch_stream, body);
+}
+
+// L1 / elastic-net twins of sgd_epoch and sgd_solve: same positional
+// arguments, then col_l1 [ncols_pad] and the credit tables cpos / cneg
+// [fa][ncols_pad] (zero-initialised by the caller, carried across epochs)
+void sgd_epoch_l1(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
+                  torch::Tensor W, torch::Tensor V, torch::Tensor WbfT,
+                  torch::Tensor partial, torch::Tensor y,
+                  torch::Tensor fold, torch::Tensor col_class,
+                  torch::Tensor col_fold, torch::Tensor col_class2,
+                  torch::Tensor col_lr, torch::Tensor col_l2,
+                  torch::Tensor fmask, torch::Tensor row_w,
+                  torch::Tensor inv_m_cpu, int64_t batch_size,
+                  int64_t loss_id, double lr_scale, double momentum,
+                  int64_t intercept_row, torch::Tensor col_l1,
+                  torch::Tensor cpos, torch::Tensor cneg) {
+    auto a = check_args(Xs, XsT, GT, W, partial, y);
+    TORCH_CHECK(batch_size % 128 == 0, "batch_size must be a mult of 128");
+    TORCH_CHECK(!inv_m_cpu.is_cuda(), "inv_m must be a CPU tensor");
+    TORCH_CHECK(inv_m_cpu.numel() >= n_batches_of(a, batch_size),
+                "inv_m shorter than the batch count");
+    auto l1 = check_l1(col_l1, cpos, cneg, W, momentum);
+    enqueue_epoch(a, Xs, XsT, GT, W, V, WbfT, partial, y, fold, col_class,
+                  col_fold, col_class2, col_lr, col_l2, fmask, row_w,
+                  (const float*)inv_m_cpu.data_ptr(), batch_size, loss_id,
+                  (float)lr_scale, momentum, intercept_row, l1,
+                  c10::hip::getCurrentHIPStream().stream(), "sgd_epoch_l1");
+}
+
+void sgd_solve_l1(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
+                  torch::Tensor W, torch::Tensor V, torch::Tensor WbfT,
+                  torch::Tensor partial, torch::Tensor y,
+                  torch::Tensor fold, torch::Tensor col_class,
+                  torch::Tensor col_fold, torch::Tensor col_class2,
+                  torch::Tensor col_lr, torch::Tensor col_l2,
+                  torch::Tensor fmask, torch::Tensor row_w,
+                  torch::Tensor inv_m_cpu, int64_t batch_size,
+                  int64_t loss_id, double momentum, int64_t intercept_row,
+                  int64_t epochs, torch::Tensor col_l1, torch::Tensor cpos,
+                  torch::Tensor cneg) {
+    auto a = check_args(Xs, XsT, GT, W, partial, y);
+    TORCH_CHECK(batch_size % 128 == 0, "batch_size must be a mult of 128");
+    TORCH_CHECK(!inv_m_cpu.is_cuda(), "inv_m must be a CPU tensor");
+    TORCH_CHECK(inv_m_cpu.numel() >= n_batches_of(a, batch_size),
+                "inv_m shorter than the batch count");
+    auto l1 = check_l1(col_l1, cpos, cneg, W, momentum);
+    const float* inv_p = (const float*)inv_m_cpu.data_ptr();
+    auto torch_stream = c10::hip::getCurrentHIPStream().stream();
+    auto body = [&](hipStream_t st) {
+        enqueue_epoch(a, Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+                      col_class, col_fold, col_class2, col_lr, col_l2,
+                      fmask, row_w, inv_p, batch_size, loss_id, 1.0f,
+                      momentum, intercept_row, l1, st, "sgd_solve_l1");
     };
     run_epochs_graphed(epochs, torch_stream, body);
 }
@@ -240,6 +358,24 @@ extern "C" hipError_t skdist_sp_sgd_step(
     const void* bval, long long uf,
     long long start, long long m, int cp, int loss_id,
     float inv_m, float lr_scale, hipStream_t stream);
+extern "C" hipError_t skdist_sp_sgd_step_l1(
+    const void* crow, const void* cidx, const void* cval,
+    void* W, void* Wb, void* s, void* h, void* hb, void* G, void* part,
+    const void* y, const void* fold, const void* row_w,
+    const void* col_class, const void* col_fold, const void* col_class2,
+    const void* col_lr, const void* col_l2,
+    const void* ufeat, const void* cptr, const void* ridx,
+    const void* bval, long long uf,
+    long long start, long long m, int cp, int loss_id,
+    float inv_m, float lr_scale,
+    const void* col_l1, void* U, void* q, void* uw, void* ul,
+    hipStream_t stream);
+extern "C" hipError_t skdist_sp_l1_flush(
+    void* W, const void* h, const void* U, void* q, void* uw, void* ul,
+    long long f, int cp, hipStream_t stream);
+extern "C" hipError_t skdist_sp_renorm_l1(
+    void* W, const void* s, void* q, void* uw, void* ul, long long f,
+    int cp, hipStream_t stream);
 extern "C" hipError_t skdist_sp_forward(
     const void* crow, const void* cidx, const void* cval,
     const void* W, const void* Wb, const void* s, const void* rows,
@@ -355,6 +491,143 @@ void sp_sgd_solve(torch::Tensor crow, torch::Tensor cidx,
         }
     };
     run_epochs_graphed(epochs, torch_stream, body);
+}
+
+// L1 state of one sparse solve: col_l1 / U [CP], q [f][CP], and with
+// the Adagrad accumulator h also uw / ul [f][CP]
+struct SpL1Args {
+    void* U; void* q; void* uw; void* ul;
+};
+
+// `vec` is the per-column f32 vector that goes with the tables (U, or
+// the scale s in the renorm); uw / ul are present exactly when `adaptive`
+SpL1Args check_sp_l1(torch::Tensor& W, bool adaptive, torch::Tensor& vec,
+                     torch::Tensor& q, torch::Tensor& uw,
+                     torch::Tensor& ul) {
+    for (auto* t : {&W, &vec, &q, &uw, &ul}) {
+        if (t->numel() == 0) continue;
+        CHECK_DEV(*t);
+        CHECK_CONT(*t);
+        TORCH_CHECK(t->scalar_type() == torch::kFloat32,
+                    "W and the L1 state are f32");
+    }
+    TORCH_CHECK(W.dim() == 2 && vec.numel() == W.size(1),
+                "per-column vector must be [cp]");
+    TORCH_CHECK(q.sizes() == W.sizes(), "q must match W");
+    if (adaptive) {
+        TORCH_CHECK(uw.sizes() == W.sizes() && ul.sizes() == W.sizes(),
+                    "adaptive L1 tables must match W");
+    } else {
+        TORCH_CHECK(uw.numel() == 0 && ul.numel() == 0,
+                    "adaptive L1 tables need the Adagrad accumulator");
+    }
+    return {vec.data_ptr(), q.data_ptr(),
+            adaptive ? uw.data_ptr() : nullptr,
+            adaptive ? ul.data_ptr() : nullptr};
+}
+
+// the Adagrad accumulator decides the mode: empty, or f32 shaped like W
+bool check_adagrad(torch::Tensor& W, torch::Tensor& h) {
+    if (h.numel() == 0) return false;
+    CHECK_DEV(h);
+    CHECK_CONT(h);
+    TORCH_CHECK(h.scalar_type() == torch::kFloat32 &&
+                h.sizes() == W.sizes(), "h must be f32 and match W");
+    return true;
+}
+
+// L1 / elastic-net twin of sp_sgd_epoch: same positional arguments, then
+// col_l1 [CP] and the L1 state (zero-initialised by the caller, carried
+// across epochs).  One call per epoch, no graph capture.
+void sp_sgd_epoch_l1(torch::Tensor crow, torch::Tensor cidx,
+                     torch::Tensor cval, torch::Tensor W, torch::Tensor Wb,
+                     torch::Tensor s, torch::Tensor h, torch::Tensor hb,
+                     torch::Tensor G, torch::Tensor part,
+                     torch::Tensor y, torch::Tensor fold,
+                     torch::Tensor row_w,
+                     torch::Tensor col_class, torch::Tensor col_fold,
+                     torch::Tensor col_class2, torch::Tensor col_lr,
+                     torch::Tensor col_l2, torch::Tensor ufeat,
+                     torch::Tensor cptr, torch::Tensor ridx,
+                     torch::Tensor bval, torch::Tensor ub_ptr_cpu,
+                     torch::Tensor inv_m_cpu, int64_t batch_size,
+                     int64_t loss_id, double lr_scale,
+                     torch::Tensor col_l1, torch::Tensor U,
+                     torch::Tensor q, torch::Tensor uw, torch::Tensor ul) {
+    for (auto* t : {&crow, &cidx, &cval, &W, &Wb, &s, &G, &part, &y,
+                    &fold, &col_class, &col_fold, &col_class2, &col_lr,
+                    &col_l2, &ufeat, &cptr, &ridx, &bval, &col_l1}) {
+        CHECK_DEV(*t);
+        CHECK_CONT(*t);
+    }
+    TORCH_CHECK(!ub_ptr_cpu.is_cuda() && !inv_m_cpu.is_cuda(),
+                "ub_ptr/inv_m must be CPU tensors");
+    TORCH_CHECK(crow.scalar_type() == torch::kInt64, "crow must be i64");
+    TORCH_CHECK(cidx.scalar_type() == torch::kInt32, "cidx must be i32");
+    TORCH_CHECK(G.scalar_type() == torch::kBFloat16, "G must be bf16");
+    const int64_t cp = W.size(1);
+    check_cp(cp);
+    TORCH_CHECK(col_l1.numel() == cp &&
+                col_l1.scalar_type() == torch::kFloat32,
+                "col_l1 must be f32 [cp]");
+    auto l1 = check_sp_l1(W, check_adagrad(W, h), U, q, uw, ul);
+    const int64_t n = crow.size(0) - 1;
+    TORCH_CHECK(G.size(0) >= std::min<int64_t>(batch_size, n) &&
+                G.size(1) == cp, "G buffer too small");
+    const int64_t nb = (n + batch_size - 1) / batch_size;
+    TORCH_CHECK(ub_ptr_cpu.numel() >= nb + 1 && inv_m_cpu.numel() >= nb,
+                "ub_ptr/inv_m shorter than the batch count");
+    const int64_t* ub = (const int64_t*)ub_ptr_cpu.data_ptr();
+    TORCH_CHECK(ub[nb] <= ufeat.numel() && ub[nb] + 1 <= cptr.numel(),
+                "ub_ptr runs past ufeat/cptr");
+    const float* inv_p = (const float*)inv_m_cpu.data_ptr();
+    auto stream = c10::hip::getCurrentHIPStream().stream();
+    int64_t bi = 0;
+    for (int64_t start = 0; start < n; start += batch_size, ++bi) {
+        const int64_t m = std::min(batch_size, n - start);
+        const int64_t ub0 = ub[bi], uf = ub[bi + 1] - ub[bi];
+        hipError_t err = skdist_sp_sgd_step_l1(
+            crow.data_ptr(), cidx.data_ptr(), cval.data_ptr(),
+            W.data_ptr(), Wb.data_ptr(), s.data_ptr(),
+            h.numel() ? h.data_ptr() : nullptr,
+            hb.numel() ? hb.data_ptr() : nullptr, G.data_ptr(),
+            part.data_ptr(), y.data_ptr(), fold.data_ptr(),
+            row_w.numel() ? row_w.data_ptr() : nullptr,
+            col_class.data_ptr(), col_fold.data_ptr(),
+            col_class2.data_ptr(), col_lr.data_ptr(), col_l2.data_ptr(),
+            (const int*)ufeat.data_ptr() + ub0,
+            (const long long*)cptr.data_ptr() + ub0,
+            ridx.data_ptr(), bval.data_ptr(), uf,
+            start, m, (int)cp, (int)loss_id, inv_p[bi],
+            (float)lr_scale, col_l1.data_ptr(), l1.U, l1.q, l1.uw, l1.ul,
+            stream);
+        TORCH_CHECK(err == hipSuccess, "sp_sgd_epoch_l1: ",
+                    hipGetErrorString(err));
+    }
+}
+
+// end-of-fit L1 flush over all (feature, column)
+void sp_l1_flush(torch::Tensor W, torch::Tensor h, torch::Tensor U,
+                 torch::Tensor q, torch::Tensor uw, torch::Tensor ul) {
+    auto l1 = check_sp_l1(W, check_adagrad(W, h), U, q, uw, ul);
+    auto stream = c10::hip::getCurrentHIPStream().stream();
+    hipError_t err = skdist_sp_l1_flush(
+        W.data_ptr(), h.numel() ? h.data_ptr() : nullptr, l1.U, l1.q,
+        l1.uw, l1.ul, W.size(0), (int)W.size(1), stream);
+    TORCH_CHECK(err == hipSuccess, "sp_l1_flush: ", hipGetErrorString(err));
+}
+
+// L1-mode renorm: W and the per-weight L1 tables change units together
+// (the caller scales the per-column U and resets s)
+void sp_renorm_l1(torch::Tensor W, torch::Tensor s, torch::Tensor q,
+                  torch::Tensor uw, torch::Tensor ul) {
+    auto l1 = check_sp_l1(W, uw.numel() > 0, s, q, uw, ul);
+    auto stream = c10::hip::getCurrentHIPStream().stream();
+    hipError_t err = skdist_sp_renorm_l1(
+        W.data_ptr(), l1.U, l1.q, l1.uw, l1.ul, W.size(0), (int)W.size(1),
+        stream);
+    TORCH_CHECK(err == hipSuccess, "sp_renorm_l1: ",
+                hipGetErrorString(err));
 }
 
 void sp_forward(torch::Tensor crow, torch::Tensor cidx,
@@ -873,10 +1146,19 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("sgd_epoch", &sgd_epoch, "one epoch of fused SGD steps");
     m.def("sp_sgd_epoch", &sp_sgd_epoch,
           "one epoch of the sparse text-scale solver");
+    m.def("sgd_epoch_l1", &sgd_epoch_l1,
+          "one epoch of fused SGD steps with the L1 update");
+    m.def("sgd_solve_l1", &sgd_solve_l1,
+          "all epochs with the L1 update (hipGraph replay)");
     m.def("sgd_solve", &sgd_solve,
           "all epochs of the dense solver (hipGraph-replayed)");
     m.def("sp_sgd_solve", &sp_sgd_solve,
           "all epochs of the sparse solver (hipGraph-replayed)");
+    m.def("sp_sgd_epoch_l1", &sp_sgd_epoch_l1,
+          "one epoch of sparse SGD steps with the lazy L1 update");
+    m.def("sp_l1_flush", &sp_l1_flush, "end-of-fit L1 flush");
+    m.def("sp_renorm_l1", &sp_renorm_l1,
+          "fold the lazy-L2 scale into W and the L1 tables");
     m.def("sp_forward", &sp_forward, "sparse decision values (scoring)");
     m.def("sp_renorm", &sp_renorm, "fold the lazy-L2 scale into W");
     m.def("score_fold", &score_fold,

@@ -266,8 +266,20 @@ extern "C" __global__ __launch_bounds__(256) void k_grad_partial(
 // ---------------------------------------------------------------------- //
 // K3: reduce partials, update W (+momentum), refresh WbfT
 // grid: (ncols_pad/128, fa), block 128
+//
+// L1 = true adds the cumulative-penalty L1 step (Tsuruoka et al. 2009;
+// eager twin: _sgd._l1_clip_torch) after the gradient step.  Per weight
+// two credits live in [fa][ncols_pad] f32 tables: cpos = u + q is what a
+// positive weight still owes, cneg = u - q what a negative one owes
+// (u: penalty that could have been applied so far, q: signed penalty
+// actually applied).  Both advance by lr * lr_scale * l1 * l1_gain per
+// step, l1_gain = 1 / (1 - momentum); a weight is clipped towards 0 by
+// its credit, never across 0, and a weight at exactly 0 stays there.
+// Every lane reads and writes only its own (row, col) entries, so no
+// lane depends on what another block writes in the same launch.
 // ---------------------------------------------------------------------- //
-extern "C" __global__ __launch_bounds__(128) void k_reduce_update(
+template <bool L1>
+static __device__ __forceinline__ void reduce_update_body(
     const float* __restrict__ partial,
     float* __restrict__ W,
     float* __restrict__ V,
@@ -276,8 +288,10 @@ extern "C" __global__ __launch_bounds__(128) void k_reduce_update(
     const float* __restrict__ col_l2,
     const unsigned char* __restrict__ fmask,  // [fa][ncols_pad] or null:
     float inv_m, float lr_scale, float momentum,  // 0 pins W to 0 (the
-    int intercept_row, int splitk, int fa, int ncols_pad)  // per-column
-{                                             // feature-subset device path)
+    int intercept_row, int splitk, int fa, int ncols_pad,  // per-column
+    const float* __restrict__ col_l1,         // feature-subset device path)
+    float* __restrict__ cpos, float* __restrict__ cneg, float l1_gain)
+{
     const int col = blockIdx.x * 128 + threadIdx.x;
     const int row = blockIdx.y;
     const long long e = (long long)row * ncols_pad + col;
@@ -296,6 +310,21 @@ extern "C" __global__ __launch_bounds__(128) void k_reduce_update(
         step = v;
     }
     wv -= step;
+    if (L1 && row != intercept_row) {
+        const float delta = col_lr[col] * lr_scale * col_l1[col] * l1_gain;
+        float cp = cpos[e] + delta;
+        float cn = cneg[e] + delta;
+        float wn = wv;
+        if (wv > 0.f) wn = fmaxf(wv - cp, 0.f);
+        else if (wv < 0.f) wn = fminf(wv + cn, 0.f);
+        const float d = wn - wv;
+        cp += d;
+        cn -= d;
+        wv = wn;
+        if (fmask != nullptr && fmask[e] == 0) { cp = 0.f; cn = 0.f; }
+        cpos[e] = cp;
+        cneg[e] = cn;
+    }
     if (fmask != nullptr && fmask[e] == 0) {
         wv = 0.f;
         if (momentum > 0.f) V[e] = 0.f;
@@ -304,10 +333,42 @@ extern "C" __global__ __launch_bounds__(128) void k_reduce_update(
     WbfT[(long long)col * fa + row] = f32_to_bf16(wv);
 }
 
+extern "C" __global__ __launch_bounds__(128) void k_reduce_update(
+    const float* __restrict__ partial, float* __restrict__ W,
+    float* __restrict__ V, __bf16* __restrict__ WbfT,
+    const float* __restrict__ col_lr, const float* __restrict__ col_l2,
+    const unsigned char* __restrict__ fmask,
+    float inv_m, float lr_scale, float momentum,
+    int intercept_row, int splitk, int fa, int ncols_pad)
+{
+    reduce_update_body<false>(partial, W, V, WbfT, col_lr, col_l2, fmask,
+                              inv_m, lr_scale, momentum, intercept_row,
+                              splitk, fa, ncols_pad, nullptr, nullptr,
+                              nullptr, 0.f);
+}
+
+extern "C" __global__ __launch_bounds__(128) void k_reduce_update_l1(
+    const float* __restrict__ partial, float* __restrict__ W,
+    float* __restrict__ V, __bf16* __restrict__ WbfT,
+    const float* __restrict__ col_lr, const float* __restrict__ col_l2,
+    const unsigned char* __restrict__ fmask,
+    float inv_m, float lr_scale, float momentum,
+    int intercept_row, int splitk, int fa, int ncols_pad,
+    const float* __restrict__ col_l1, float* __restrict__ cpos,
+    float* __restrict__ cneg, float l1_gain)
+{
+    reduce_update_body<true>(partial, W, V, WbfT, col_lr, col_l2, fmask,
+                             inv_m, lr_scale, momentum, intercept_row,
+                             splitk, fa, ncols_pad, col_l1, cpos, cneg,
+                             l1_gain);
+}
+
 // ---------------------------------------------------------------------- //
-// host launcher
+// host launcher.  col_l1 == null is the L2-only step (k_reduce_update);
+// otherwise cpos/cneg are the [fa][ncols_pad] L1 credit tables and K3 is
+// k_reduce_update_l1.  K1 and K2 are shared.
 // ---------------------------------------------------------------------- //
-extern "C" hipError_t skdist_sgd_step(
+static hipError_t sgd_step_impl(
     const void* Xs, const void* XsT, const void* WbfT_in,
     void* GT, void* W, void* V, void* WbfT, void* partial,
     const void* y, const void* fold,
@@ -318,6 +379,7 @@ extern "C" hipError_t skdist_sgd_step(
     long long fa_store, int fa, int ncols_pad,
     int gt_stride, int splitk, int loss_id,
     float lr_scale, float momentum, int intercept_row,
+    const void* col_l1, void* cpos, void* cneg,
     hipStream_t stream)
 {
     const int m_pad = (int)((m + BM - 1) / BM) * BM;
@@ -345,16 +407,74 @@ extern "C" hipError_t skdist_sgd_step(
     }
     {
         dim3 grid(ncols_pad / 128, fa);
-        hipLaunchKernelGGL(k_reduce_update, grid, dim3(128), 0, stream,
-                           (const float*)partial, (float*)W, (float*)V,
-                           (__bf16*)WbfT, (const float*)col_lr,
-                           (const float*)col_l2,
-                           (const unsigned char*)fmask, inv_m,
-                           lr_scale, momentum, intercept_row, splitk, fa,
-                           ncols_pad);
+        if (col_l1 == nullptr) {
+            hipLaunchKernelGGL(k_reduce_update, grid, dim3(128), 0, stream,
+                               (const float*)partial, (float*)W, (float*)V,
+                               (__bf16*)WbfT, (const float*)col_lr,
+                               (const float*)col_l2,
+                               (const unsigned char*)fmask, inv_m,
+                               lr_scale, momentum, intercept_row, splitk,
+                               fa, ncols_pad);
+        } else {
+            hipLaunchKernelGGL(k_reduce_update_l1, grid, dim3(128), 0,
+                               stream,
+                               (const float*)partial, (float*)W, (float*)V,
+                               (__bf16*)WbfT, (const float*)col_lr,
+                               (const float*)col_l2,
+                               (const unsigned char*)fmask, inv_m,
+                               lr_scale, momentum, intercept_row, splitk,
+                               fa, ncols_pad, (const float*)col_l1,
+                               (float*)cpos, (float*)cneg,
+                               1.f / (1.f - momentum));
+        }
         HIP_CHECK(hipGetLastError());
     }
     return hipSuccess;
+}
+
+extern "C" hipError_t skdist_sgd_step(
+    const void* Xs, const void* XsT, const void* WbfT_in,
+    void* GT, void* W, void* V, void* WbfT, void* partial,
+    const void* y, const void* fold,
+    const void* col_class, const void* col_fold, const void* col_class2,
+    const void* col_lr, const void* col_l2, const void* fmask,
+    const void* row_w, float inv_m,
+    long long start, long long m, long long n, long long n_pad,
+    long long fa_store, int fa, int ncols_pad,
+    int gt_stride, int splitk, int loss_id,
+    float lr_scale, float momentum, int intercept_row,
+    hipStream_t stream)
+{
+    return sgd_step_impl(Xs, XsT, WbfT_in, GT, W, V, WbfT, partial, y,
+                         fold, col_class, col_fold, col_class2, col_lr,
+                         col_l2, fmask, row_w, inv_m, start, m, n, n_pad,
+                         fa_store, fa, ncols_pad, gt_stride, splitk,
+                         loss_id, lr_scale, momentum, intercept_row,
+                         nullptr, nullptr, nullptr, stream);
+}
+
+extern "C" hipError_t skdist_sgd_step_l1(
+    const void* Xs, const void* XsT, const void* WbfT_in,
+    void* GT, void* W, void* V, void* WbfT, void* partial,
+    const void* y, const void* fold,
+    const void* col_class, const void* col_fold, const void* col_class2,
+    const void* col_lr, const void* col_l2, const void* fmask,
+    const void* row_w, float inv_m,
+    long long start, long long m, long long n, long long n_pad,
+    long long fa_store, int fa, int ncols_pad,
+    int gt_stride, int splitk, int loss_id,
+    float lr_scale, float momentum, int intercept_row,
+    const void* col_l1, void* cpos, void* cneg,
+    hipStream_t stream)
+{
+    if (col_l1 == nullptr || cpos == nullptr || cneg == nullptr)
+        return hipErrorInvalidValue;
+    return sgd_step_impl(Xs, XsT, WbfT_in, GT, W, V, WbfT, partial, y,
+                         fold, col_class, col_fold, col_class2, col_lr,
+                         col_l2, fmask, row_w, inv_m, start, m, n, n_pad,
+                         fa_store, fa, ncols_pad, gt_stride, splitk,
+                         loss_id, lr_scale, momentum, intercept_row,
+                         col_l1, cpos, cneg, stream);
 }
 
 // ---------------------------------------------------------------------- //

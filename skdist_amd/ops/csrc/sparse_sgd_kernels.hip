@@ -21,6 +21,25 @@
 //     => W_true' = (1 - lr*l2) W_true - lr * g * inv_m            (exactly
 //        the dense k_reduce_update step, momentum 0)
 //
+// L1 / elastic-net (the *_l1 kernels; eager twin in _sparse_sgd.py): the
+// cumulative-penalty rule (Tsuruoka et al. 2009) applied LAZILY, in the
+// stored units above (W_true = s * W; every L1 quantity below is a
+// stored-unit one, so it also shrinks with the lazy L2 scale):
+//
+//     U[c]   += lr_c * lrs * l1_c / s'[c]          per step (K2b_l1)
+//     u(j,c)  = U[c]                               adaptive off
+//     u(j,c) += (U[c] - Ulast(j,c)) * rsqrt(H(j,c) + 1e-12)  at a touch,
+//               nothing while H(j,c) == 0          adaptive on
+//     w > 0: w' = max(0, w - (u + q));  w < 0: w' = min(0, w + (u - q));
+//     w == 0 stays;  q += w' - w
+//
+// A weight is touched (brought up to date) by k_sp_l1_catchup before the
+// forward of every batch that holds its feature, by k_sp_update_l1 after
+// its gradient step, and by k_sp_l1_flush once at the end of the fit.
+// Between touches neither w's gradient step nor H changes, so one clip
+// by the accumulated credit equals the per-step clips it replaces.
+// Extra tables [f][CP] f32: Q (always), Uw and Ul (adaptive only).
+//
 // Determinism: no atomics anywhere.  K1 owns (row, column) — the dot
 // product walks the row's nnz in CSR order; K3 owns (feature, column) —
 // the gradient walks the feature's batch rows in CSC order; K2 reduces
@@ -147,11 +166,13 @@ extern "C" __global__ __launch_bounds__(256) void k_sp_colsum(
 // K2b: reduce chunks -> intercept update + lazy-scale advance
 // grid: ceil(CP/256), block 256.  With `hb` non-null the intercept step
 // is Adagrad-normalized (hb accumulates the squared mean-gradient).
-extern "C" __global__ __launch_bounds__(256) void k_sp_bias_scale(
+template <bool L1>
+static __device__ __forceinline__ void sp_bias_scale_body(
     const float* __restrict__ part, float* __restrict__ Wb,
     float* __restrict__ s, float* __restrict__ hb,
     const float* __restrict__ col_lr, const float* __restrict__ col_l2,
-    int n_chunks, int cp, float inv_m, float lr_scale)
+    int n_chunks, int cp, float inv_m, float lr_scale,
+    const float* __restrict__ col_l1, float* __restrict__ U)
 {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= cp) return;
@@ -174,7 +195,52 @@ extern "C" __global__ __launch_bounds__(256) void k_sp_bias_scale(
         step = lr * g * __frsqrt_rn(h + 1e-12f);
     }
     Wb[c] -= step;                            // no L2 on the intercept
-    s[c] *= (1.f - lr * col_l2[c]);          // lazy decay of all of W
+    const float sn = s[c] * (1.f - lr * col_l2[c]);
+    s[c] = sn;                                // lazy decay of all of W
+    if (L1) U[c] += lr * col_l1[c] / sn;      // stored-unit L1 threshold
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_sp_bias_scale(
+    const float* __restrict__ part, float* __restrict__ Wb,
+    float* __restrict__ s, float* __restrict__ hb,
+    const float* __restrict__ col_lr, const float* __restrict__ col_l2,
+    int n_chunks, int cp, float inv_m, float lr_scale)
+{
+    sp_bias_scale_body<false>(part, Wb, s, hb, col_lr, col_l2, n_chunks,
+                              cp, inv_m, lr_scale, nullptr, nullptr);
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_sp_bias_scale_l1(
+    const float* __restrict__ part, float* __restrict__ Wb,
+    float* __restrict__ s, float* __restrict__ hb,
+    const float* __restrict__ col_lr, const float* __restrict__ col_l2,
+    int n_chunks, int cp, float inv_m, float lr_scale,
+    const float* __restrict__ col_l1, float* __restrict__ U)
+{
+    sp_bias_scale_body<true>(part, Wb, s, hb, col_lr, col_l2, n_chunks,
+                             cp, inv_m, lr_scale, col_l1, U);
+}
+
+// One touch of weight e = (j, c): bring its L1 credit up to the column's
+// U, clip, book what was applied.  `uw` / `ul` null = adaptive off.
+static __device__ __forceinline__ float sp_l1_touch(
+    float w, long long e, float Uc, const float* __restrict__ h,
+    float* __restrict__ q, float* __restrict__ uw, float* __restrict__ ul)
+{
+    float u = Uc;
+    if (uw != nullptr) {
+        u = uw[e];
+        const float hv = h[e];
+        if (hv > 0.f) u += (Uc - ul[e]) * __frsqrt_rn(hv + 1e-12f);
+        uw[e] = u;
+        ul[e] = Uc;
+    }
+    const float qv = q[e];
+    float wn = w;
+    if (w > 0.f) wn = fmaxf(w - (u + qv), 0.f);
+    else if (w < 0.f) wn = fminf(w + (u - qv), 0.f);
+    q[e] = qv + (wn - w);
+    return wn;
 }
 
 // ---------------------------------------------------------------------- //
@@ -186,7 +252,8 @@ extern "C" __global__ __launch_bounds__(256) void k_sp_bias_scale(
 // the lazy L2 scale path is untouched, so regularization stays exactly
 // the dense solver's per-step decay.
 // ---------------------------------------------------------------------- //
-extern "C" __global__ __launch_bounds__(256) void k_sp_update(
+template <bool L1>
+static __device__ __forceinline__ void sp_update_body(
     const int* __restrict__ ufeat,   // [uf]
     const long long* __restrict__ cptr,  // [uf+1]
     const int* __restrict__ ridx,    // row-local
@@ -196,7 +263,9 @@ extern "C" __global__ __launch_bounds__(256) void k_sp_update(
     float* __restrict__ h,           // [f][CP] Adagrad accum, or null
     const float* __restrict__ s,     // [CP] (post-K2b value)
     const float* __restrict__ col_lr,
-    long long uf, int cp, float inv_m, float lr_scale)
+    long long uf, int cp, float inv_m, float lr_scale,
+    const float* __restrict__ U,     // [CP] (post-K2b value)
+    float* __restrict__ q, float* __restrict__ uw, float* __restrict__ ul)
 {
     const int tc = g_tc(cp);
     const int fpb = 256 / tc;
@@ -227,8 +296,76 @@ extern "C" __global__ __launch_bounds__(256) void k_sp_update(
         h[e] = hv;
         step *= __frsqrt_rn(hv + 1e-12f);
     }
-    W[e] -= step / s[c];
+    if (L1) {
+        const float w = W[e] - step / s[c];
+        W[e] = sp_l1_touch(w, e, U[c], h, q, uw, ul);
+    } else {
+        W[e] -= step / s[c];
     }
+    }
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_sp_update(
+    const int* __restrict__ ufeat, const long long* __restrict__ cptr,
+    const int* __restrict__ ridx, const float* __restrict__ bval,
+    const __bf16* __restrict__ G, float* __restrict__ W,
+    float* __restrict__ h, const float* __restrict__ s,
+    const float* __restrict__ col_lr,
+    long long uf, int cp, float inv_m, float lr_scale)
+{
+    sp_update_body<false>(ufeat, cptr, ridx, bval, G, W, h, s, col_lr, uf,
+                          cp, inv_m, lr_scale, nullptr, nullptr, nullptr,
+                          nullptr);
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_sp_update_l1(
+    const int* __restrict__ ufeat, const long long* __restrict__ cptr,
+    const int* __restrict__ ridx, const float* __restrict__ bval,
+    const __bf16* __restrict__ G, float* __restrict__ W,
+    float* __restrict__ h, const float* __restrict__ s,
+    const float* __restrict__ col_lr,
+    long long uf, int cp, float inv_m, float lr_scale,
+    const float* __restrict__ U, float* __restrict__ q,
+    float* __restrict__ uw, float* __restrict__ ul)
+{
+    sp_update_body<true>(ufeat, cptr, ridx, bval, G, W, h, s, col_lr, uf,
+                         cp, inv_m, lr_scale, U, q, uw, ul);
+}
+
+// L1 catch-up: touch every (batch feature, column) BEFORE the forward, so
+// k_sp_fwd reads weights that carry all the penalty accrued since their
+// last touch.  grid: (ceil(uf / fpb), CP / TC), block 256 (as K3).
+extern "C" __global__ __launch_bounds__(256) void k_sp_l1_catchup(
+    const int* __restrict__ ufeat, float* __restrict__ W,
+    const float* __restrict__ h, const float* __restrict__ U,
+    float* __restrict__ q, float* __restrict__ uw, float* __restrict__ ul,
+    long long uf, int cp)
+{
+    const int tc = g_tc(cp);
+    const int fpb = 256 / tc;
+    const int c = blockIdx.y * tc + (threadIdx.x % tc);
+    if (c >= cp) return;
+    const float Uc = U[c];
+    const long long stride = (long long)gridDim.x * fpb;
+    for (long long si = (long long)blockIdx.x * fpb + threadIdx.x / tc;
+         si < uf; si += stride) {
+        const long long e = (long long)ufeat[si] * cp + c;
+        W[e] = sp_l1_touch(W[e], e, Uc, h, q, uw, ul);
+    }
+}
+
+// L1 flush: touch ALL (feature, column) once at the end of the fit (and
+// nothing else: a feature stored in a single row gets the penalty of
+// every later step here).  grid: (f, CP/256), block 256
+extern "C" __global__ __launch_bounds__(256) void k_sp_l1_flush(
+    float* __restrict__ W, const float* __restrict__ h,
+    const float* __restrict__ U, float* __restrict__ q,
+    float* __restrict__ uw, float* __restrict__ ul, long long f, int cp)
+{
+    const int c = blockIdx.y * 256 + threadIdx.x;
+    if (c >= cp) return;
+    const long long e = (long long)blockIdx.x * cp + c;
+    W[e] = sp_l1_touch(W[e], e, U[c], h, q, uw, ul);
 }
 
 // fold the scale into W when it drifts far from 1 (rare; keeps /s[c]
@@ -240,6 +377,25 @@ extern "C" __global__ __launch_bounds__(256) void k_sp_renorm(
     const int c = blockIdx.y * 256 + threadIdx.x;
     if (c >= cp) return;
     W[(long long)blockIdx.x * cp + c] *= s[c];
+}
+
+// L1 mode: the per-weight stored-unit L1 tables change units with W
+// (the per-column U is scaled by the caller).  uw / ul null = adaptive off
+extern "C" __global__ __launch_bounds__(256) void k_sp_renorm_l1(
+    float* __restrict__ W, const float* __restrict__ s,
+    float* __restrict__ q, float* __restrict__ uw, float* __restrict__ ul,
+    long long f, int cp)
+{
+    const int c = blockIdx.y * 256 + threadIdx.x;
+    if (c >= cp) return;
+    const long long e = (long long)blockIdx.x * cp + c;
+    const float sc = s[c];
+    W[e] *= sc;
+    q[e] *= sc;
+    if (uw != nullptr) {
+        uw[e] *= sc;
+        ul[e] *= sc;
+    }
 }
 
 // ---------------------------------------------------------------------- //
@@ -267,7 +423,10 @@ static inline void sp_fwd_launch(
                        (__bf16*)G, (float*)Z, start, m, cp, loss_id);
 }
 
-extern "C" hipError_t skdist_sp_sgd_step(
+// col_l1 == null: the L2-only step.  Otherwise U [CP] and q [f][CP]
+// (and uw, ul [f][CP] when h is set) carry the L1 state, the catch-up
+// runs first and K2b / K3 are their _l1 variants.
+static hipError_t sp_sgd_step_impl(
     const void* crow, const void* cidx, const void* cval,
     void* W, void* Wb, void* s, void* h, void* hb, void* G, void* part,
     const void* y, const void* fold, const void* row_w,
@@ -276,8 +435,23 @@ extern "C" hipError_t skdist_sp_sgd_step(
     const void* ufeat, const void* cptr, const void* ridx,
     const void* bval, long long uf,
     long long start, long long m, int cp, int loss_id,
-    float inv_m, float lr_scale, hipStream_t stream)
+    float inv_m, float lr_scale,
+    const void* col_l1, void* U, void* q, void* uw, void* ul,
+    hipStream_t stream)
 {
+    const bool l1 = col_l1 != nullptr;
+    const int tc3 = cp >= 256 ? 256 : cp;
+    const int fpb3 = 256 / tc3;
+    long long gx3 = (uf + fpb3 - 1) / fpb3;
+    if (gx3 > 2048) gx3 = 2048;
+    const dim3 grid3((unsigned)gx3, (unsigned)((cp + tc3 - 1) / tc3));
+    if (l1 && uf > 0) {
+        hipLaunchKernelGGL(k_sp_l1_catchup, grid3, dim3(256), 0, stream,
+                           (const int*)ufeat, (float*)W, (const float*)h,
+                           (const float*)U, (float*)q, (float*)uw,
+                           (float*)ul, uf, cp);
+        HIP_CHECK(hipGetLastError());
+    }
     sp_fwd_launch(crow, cidx, cval, W, Wb, s, y, fold, row_w, col_class,
                   col_fold, col_class2, nullptr, G, nullptr, start, m, cp,
                   loss_id, stream);
@@ -294,28 +468,109 @@ extern "C" hipError_t skdist_sp_sgd_step(
     }
     {
         dim3 grid((unsigned)((cp + 255) / 256));
-        hipLaunchKernelGGL(k_sp_bias_scale, grid, dim3(256), 0, stream,
-                           (const float*)part, (float*)Wb, (float*)s,
-                           (float*)hb,
-                           (const float*)col_lr, (const float*)col_l2,
-                           nch, cp, inv_m, lr_scale);
+        if (!l1)
+            hipLaunchKernelGGL(k_sp_bias_scale, grid, dim3(256), 0, stream,
+                               (const float*)part, (float*)Wb, (float*)s,
+                               (float*)hb,
+                               (const float*)col_lr, (const float*)col_l2,
+                               nch, cp, inv_m, lr_scale);
+        else
+            hipLaunchKernelGGL(k_sp_bias_scale_l1, grid, dim3(256), 0,
+                               stream,
+                               (const float*)part, (float*)Wb, (float*)s,
+                               (float*)hb,
+                               (const float*)col_lr, (const float*)col_l2,
+                               nch, cp, inv_m, lr_scale,
+                               (const float*)col_l1, (float*)U);
         HIP_CHECK(hipGetLastError());
     }
     if (uf > 0) {
-        const int tc = cp >= 256 ? 256 : cp;
-        const int fpb = 256 / tc;
-        long long gx = (uf + fpb - 1) / fpb;
-        if (gx > 2048) gx = 2048;
-        dim3 grid((unsigned)gx, (unsigned)((cp + tc - 1) / tc));
-        hipLaunchKernelGGL(k_sp_update, grid, dim3(256), 0, stream,
-                           (const int*)ufeat, (const long long*)cptr,
-                           (const int*)ridx, (const float*)bval,
-                           (const __bf16*)G, (float*)W, (float*)h,
-                           (const float*)s,
-                           (const float*)col_lr, uf, cp, inv_m, lr_scale);
+        if (!l1)
+            hipLaunchKernelGGL(k_sp_update, grid3, dim3(256), 0, stream,
+                               (const int*)ufeat, (const long long*)cptr,
+                               (const int*)ridx, (const float*)bval,
+                               (const __bf16*)G, (float*)W, (float*)h,
+                               (const float*)s, (const float*)col_lr, uf,
+                               cp, inv_m, lr_scale);
+        else
+            hipLaunchKernelGGL(k_sp_update_l1, grid3, dim3(256), 0, stream,
+                               (const int*)ufeat, (const long long*)cptr,
+                               (const int*)ridx, (const float*)bval,
+                               (const __bf16*)G, (float*)W, (float*)h,
+                               (const float*)s, (const float*)col_lr, uf,
+                               cp, inv_m, lr_scale, (const float*)U,
+                               (float*)q, (float*)uw, (float*)ul);
         HIP_CHECK(hipGetLastError());
     }
     return hipSuccess;
+}
+
+extern "C" hipError_t skdist_sp_sgd_step(
+    const void* crow, const void* cidx, const void* cval,
+    void* W, void* Wb, void* s, void* h, void* hb, void* G, void* part,
+    const void* y, const void* fold, const void* row_w,
+    const void* col_class, const void* col_fold, const void* col_class2,
+    const void* col_lr, const void* col_l2,
+    const void* ufeat, const void* cptr, const void* ridx,
+    const void* bval, long long uf,
+    long long start, long long m, int cp, int loss_id,
+    float inv_m, float lr_scale, hipStream_t stream)
+{
+    return sp_sgd_step_impl(crow, cidx, cval, W, Wb, s, h, hb, G, part, y,
+                            fold, row_w, col_class, col_fold, col_class2,
+                            col_lr, col_l2, ufeat, cptr, ridx, bval, uf,
+                            start, m, cp, loss_id, inv_m, lr_scale,
+                            nullptr, nullptr, nullptr, nullptr, nullptr,
+                            stream);
+}
+
+extern "C" hipError_t skdist_sp_sgd_step_l1(
+    const void* crow, const void* cidx, const void* cval,
+    void* W, void* Wb, void* s, void* h, void* hb, void* G, void* part,
+    const void* y, const void* fold, const void* row_w,
+    const void* col_class, const void* col_fold, const void* col_class2,
+    const void* col_lr, const void* col_l2,
+    const void* ufeat, const void* cptr, const void* ridx,
+    const void* bval, long long uf,
+    long long start, long long m, int cp, int loss_id,
+    float inv_m, float lr_scale,
+    const void* col_l1, void* U, void* q, void* uw, void* ul,
+    hipStream_t stream)
+{
+    // the adaptive tables go with the Adagrad accumulator, both or none
+    if (col_l1 == nullptr || U == nullptr || q == nullptr ||
+        (h != nullptr) != (uw != nullptr) ||
+        (uw != nullptr) != (ul != nullptr))
+        return hipErrorInvalidValue;
+    return sp_sgd_step_impl(crow, cidx, cval, W, Wb, s, h, hb, G, part, y,
+                            fold, row_w, col_class, col_fold, col_class2,
+                            col_lr, col_l2, ufeat, cptr, ridx, bval, uf,
+                            start, m, cp, loss_id, inv_m, lr_scale,
+                            col_l1, U, q, uw, ul, stream);
+}
+
+extern "C" hipError_t skdist_sp_l1_flush(
+    void* W, const void* h, const void* U, void* q, void* uw, void* ul,
+    long long f, int cp, hipStream_t stream)
+{
+    if (f == 0) return hipSuccess;
+    dim3 grid((unsigned)f, (unsigned)((cp + 255) / 256));
+    hipLaunchKernelGGL(k_sp_l1_flush, grid, dim3(256), 0, stream,
+                       (float*)W, (const float*)h, (const float*)U,
+                       (float*)q, (float*)uw, (float*)ul, f, cp);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t skdist_sp_renorm_l1(
+    void* W, const void* s, void* q, void* uw, void* ul, long long f,
+    int cp, hipStream_t stream)
+{
+    if (f == 0) return hipSuccess;
+    dim3 grid((unsigned)f, (unsigned)((cp + 255) / 256));
+    hipLaunchKernelGGL(k_sp_renorm_l1, grid, dim3(256), 0, stream,
+                       (float*)W, (const float*)s, (float*)q, (float*)uw,
+                       (float*)ul, f, cp);
+    return hipGetLastError();
 }
 
 extern "C" hipError_t skdist_sp_forward(

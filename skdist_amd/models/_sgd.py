@@ -604,18 +604,22 @@ def _score_fold_hip(ds, Wf, rows, mode, metric):
     yf[:m] = ds.y_float.index_select(0, rows)
     WbfT = torch.zeros(ncp, fa, dtype=ds.comp_dtype, device=device)
     WbfT[:ncols] = Wf.t()
-    nstat = 2 if mode == 0 else 3
+    nstat = 2 if mode == 0 else 1
     stats = torch.zeros(ncp * nstat, dtype=torch.float32, device=device)
     require_hip().score_fold(Xb.contiguous(), WbfT.contiguous(), yf,
                              stats, mode)
     sh = stats.cpu().numpy().reshape(ncp, nstat)[:ncols]
     if mode == 0:
         return sh[:, 0] / np.clip(sh[:, 1], 1, None)
-    sse, sy, syy = sh[:, 0], sh[:, 1], sh[:, 2]
+    sse = sh[:, 0].astype(np.float64)
     if metric == "neg_mean_squared_error":
         return -sse / max(m, 1)
-    sst = syy - sy * sy / max(m, 1)
-    return 1.0 - sse / np.clip(sst, 1e-12, None)
+    # the total sum of squares is the same for every column: centred and
+    # summed in float64 from the fold's y (in fp32, syy - sy*sy/m cancels
+    # to nothing once mean(y) is large against std(y))
+    yd = yf[:m].to(torch.float64)
+    sst = float(((yd - yd.mean()) ** 2).sum()) if m else 0.0
+    return 1.0 - sse / max(sst, 1e-12)
 
 
 class _MetricState:

@@ -41,13 +41,58 @@ namespace {
 #define CHECK_DEV(t) TORCH_CHECK((t).is_cuda(), #t " must be on the GPU")
 #define CHECK_CONT(t) TORCH_CHECK((t).is_contiguous(), #t " not contiguous")
 
+// ---- argument checks of the bindings.  The launchers take void*, so
+// every tensor that reaches one is first pinned to the device, layout and
+// dtype its kernel reads; a binding launches nothing on empty work.
+void check_t(const torch::Tensor& t, torch::ScalarType dt,
+             const char* name) {
+    TORCH_CHECK(t.is_cuda(), name, " must be on the GPU");
+    TORCH_CHECK(t.is_contiguous(), name, " not contiguous");
+    TORCH_CHECK(t.scalar_type() == dt, name, " must be ", dt);
+}
+
+void check_vec(const torch::Tensor& t, torch::ScalarType dt, int64_t len,
+               const char* name) {
+    check_t(t, dt, name);
+    TORCH_CHECK(t.numel() == len, name, " must have ", len, " elements");
+}
+
+void check_2d(const torch::Tensor& t, torch::ScalarType dt, int64_t rows,
+              int64_t cols, const char* name) {
+    check_t(t, dt, name);
+    TORCH_CHECK(t.dim() == 2 && t.size(0) == rows && t.size(1) == cols,
+                name, " must be [", rows, ", ", cols, "]");
+}
+
 struct StepArgs {
     int64_t n_pad, fa, fa_store, ncols_pad, gt_stride, splitk, n;
 };
 
-StepArgs check_args(torch::Tensor& Xs, torch::Tensor& XsT,
-                    torch::Tensor& GT, torch::Tensor& W,
-                    torch::Tensor& partial, torch::Tensor& y) {
+// Every tensor of one dense SGD step (K1+K2+K3), checked against what the
+// kernels index: shared by sgd_step and the epoch / solve entries with and
+// without L1.  `rows` is the largest row count one step covers (m for
+// sgd_step, the batch size otherwise); V, fmask and row_w may be empty.
+StepArgs check_step_tensors(
+    const torch::Tensor& Xs, const torch::Tensor& XsT,
+    const torch::Tensor& GT, const torch::Tensor& W, const torch::Tensor& V,
+    const torch::Tensor& WbfT, const torch::Tensor& partial,
+    const torch::Tensor& y, const torch::Tensor& fold,
+    const torch::Tensor& col_class, const torch::Tensor& col_fold,
+    const torch::Tensor& col_class2, const torch::Tensor& col_lr,
+    const torch::Tensor& col_l2, const torch::Tensor& fmask,
+    const torch::Tensor& row_w, int64_t rows, double momentum,
+    int64_t intercept_row) {
+    const auto bf16 = torch::kBFloat16;
+    const auto f32 = torch::kFloat32;
+    const auto i32 = torch::kInt32;
+    check_t(Xs, bf16, "Xs");
+    check_t(XsT, bf16, "XsT");
+    check_t(GT, bf16, "GT");
+    check_t(W, f32, "W");
+    check_t(partial, f32, "partial");
+    TORCH_CHECK(Xs.dim() == 2 && XsT.dim() == 2 && GT.dim() == 2 &&
+                W.dim() == 2, "Xs, XsT, GT and W must be 2-D");
+    TORCH_CHECK(partial.dim() == 3, "partial must be [splitk, fa, ncols_pad]");
     StepArgs a;
     a.n_pad = Xs.size(0);
     a.fa = Xs.size(1);
@@ -55,15 +100,61 @@ StepArgs check_args(torch::Tensor& Xs, torch::Tensor& XsT,
     a.ncols_pad = W.size(1);
     a.gt_stride = GT.size(1);
     a.splitk = partial.size(0);
-    a.n = y.size(0);
-    TORCH_CHECK(a.fa % 32 == 0, "fa must be a multiple of 32");
-    TORCH_CHECK(a.n_pad % 128 == 0, "n_pad must be a multiple of 128");
+    a.n = y.numel();
+    TORCH_CHECK(a.fa >= 32 && a.fa % 32 == 0,
+                "fa must be a multiple of 32");
+    TORCH_CHECK(a.n_pad >= 128 && a.n_pad % 128 == 0,
+                "n_pad must be a multiple of 128");
     TORCH_CHECK(a.fa_store % 128 == 0, "fa_store must be a multiple of 128");
-    TORCH_CHECK(a.ncols_pad % 128 == 0, "ncols_pad must be a mult of 128");
-    TORCH_CHECK(Xs.scalar_type() == torch::kBFloat16, "Xs must be bf16");
+    TORCH_CHECK(a.fa_store >= a.fa, "XsT must have at least fa rows");
+    TORCH_CHECK(a.ncols_pad >= 128 && a.ncols_pad % 128 == 0,
+                "ncols_pad must be a mult of 128");
     TORCH_CHECK(XsT.size(1) == a.n_pad, "XsT shape mismatch");
     TORCH_CHECK(W.size(0) == a.fa, "W rows != fa");
+    TORCH_CHECK(a.splitk >= 1, "splitk must be >= 1");
+    TORCH_CHECK(partial.size(1) == a.fa && partial.size(2) == a.ncols_pad,
+                "partial must be [splitk, fa, ncols_pad]");
+    check_2d(WbfT, bf16, a.ncols_pad, a.fa, "WbfT");
+    TORCH_CHECK(rows >= 1, "a step needs at least one row");
+    const int64_t rows_pad = (rows + 127) / 128 * 128;
+    TORCH_CHECK(GT.size(0) == a.ncols_pad && a.gt_stride >= rows_pad &&
+                a.gt_stride % 8 == 0,
+                "GT must be [ncols_pad, gt_stride >= ", rows_pad,
+                "] with gt_stride a multiple of 8");
+    TORCH_CHECK(a.n >= 1 && a.n <= a.n_pad, "y must have 1..n_pad elements");
+    check_vec(y, f32, a.n, "y");
+    check_vec(fold, i32, a.n, "fold");
+    check_vec(col_class, i32, a.ncols_pad, "col_class");
+    check_vec(col_fold, i32, a.ncols_pad, "col_fold");
+    check_vec(col_class2, i32, a.ncols_pad, "col_class2");
+    check_vec(col_lr, f32, a.ncols_pad, "col_lr");
+    check_vec(col_l2, f32, a.ncols_pad, "col_l2");
+    if (row_w.numel() > 0) check_vec(row_w, f32, a.n, "row_w");
+    if (fmask.numel() > 0)
+        check_2d(fmask, torch::kUInt8, a.fa, a.ncols_pad, "fmask");
+    if (V.numel() > 0) {
+        check_t(V, f32, "V");
+        TORCH_CHECK(V.sizes() == W.sizes(), "V must be empty or match W");
+    } else {
+        TORCH_CHECK(!(momentum > 0.0), "momentum > 0 needs V");
+    }
+    TORCH_CHECK(intercept_row >= 0 && intercept_row < a.fa,
+                "intercept_row must be in [0, fa)");
     return a;
+}
+
+// the epoch / solve entries walk y in batches of batch_size rows and read
+// one 1/m (or 1/sum(w)) per batch from a CPU f32 tensor
+void check_batches(const StepArgs& a, int64_t batch_size,
+                   const torch::Tensor& inv_m_cpu) {
+    TORCH_CHECK(batch_size >= 128 && batch_size % 128 == 0,
+                "batch_size must be a mult of 128");
+    TORCH_CHECK(!inv_m_cpu.is_cuda(), "inv_m must be a CPU tensor");
+    TORCH_CHECK(inv_m_cpu.scalar_type() == torch::kFloat32 &&
+                inv_m_cpu.is_contiguous(),
+                "inv_m must be a contiguous f32 tensor");
+    TORCH_CHECK(inv_m_cpu.numel() >= (a.n + batch_size - 1) / batch_size,
+                "inv_m shorter than the batch count");
 }
 
 void sgd_step(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
@@ -75,12 +166,16 @@ void sgd_step(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
               torch::Tensor fmask, torch::Tensor row_w,
               int64_t start, int64_t m, int64_t loss_id, double lr_scale,
               double momentum, int64_t intercept_row, double inv_m) {
-    for (auto* t : {&Xs, &XsT, &GT, &W, &WbfT, &partial, &y, &fold,
-                    &col_class, &col_fold, &col_lr, &col_l2}) {
-        CHECK_DEV(*t);
-        CHECK_CONT(*t);
-    }
-    auto a = check_args(Xs, XsT, GT, W, partial, y);
+    TORCH_CHECK(m >= 1, "m must be >= 1");
+    auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+                                col_class, col_fold, col_class2, col_lr,
+                                col_l2, fmask, row_w, m, momentum,
+                                intercept_row);
+    // K2 stages 16 B chunks of XsT from column `start` on
+    TORCH_CHECK(start >= 0 && start % 8 == 0,
+                "start must be a non-negative multiple of 8");
+    TORCH_CHECK(start + (m + 127) / 128 * 128 <= a.n_pad,
+                "start + m_pad must be <= n_pad");
     const bool has_V = V.numel() > 0;
     auto stream = c10::hip::getCurrentHIPStream().stream();
     hipError_t err = skdist_sgd_step(
@@ -236,10 +331,6 @@ void enqueue_epoch(const StepArgs& a, torch::Tensor& Xs, torch::Tensor& XsT,
     }
 }
 
-int64_t n_batches_of(const StepArgs& a, int64_t batch_size) {
-    return (a.n + batch_size - 1) / batch_size;
-}
-
 // one whole epoch: the minibatch loop runs in C++ so the hot path costs
 // one pybind crossing per epoch instead of one per step
 void sgd_epoch(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
@@ -252,9 +343,11 @@ void sgd_epoch(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                torch::Tensor inv_m_cpu,  // [n_batches] f32 on CPU
                int64_t batch_size, int64_t loss_id, double lr_scale,
                double momentum, int64_t intercept_row) {
-    auto a = check_args(Xs, XsT, GT, W, partial, y);
-    TORCH_CHECK(batch_size % 128 == 0, "batch_size must be a mult of 128");
-    TORCH_CHECK(!inv_m_cpu.is_cuda(), "inv_m must be a CPU tensor");
+    auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+                                col_class, col_fold, col_class2, col_lr,
+                                col_l2, fmask, row_w, batch_size, momentum,
+                                intercept_row);
+    check_batches(a, batch_size, inv_m_cpu);
     enqueue_epoch(a, Xs, XsT, GT, W, V, WbfT, partial, y, fold, col_class,
                   col_fold, col_class2, col_lr, col_l2, fmask, row_w,
                   (const float*)inv_m_cpu.data_ptr(), batch_size, loss_id,
@@ -274,8 +367,11 @@ void sgd_solve(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                torch::Tensor inv_m_cpu, int64_t batch_size,
                int64_t loss_id, double momentum, int64_t intercept_row,
                int64_t epochs) {
-    auto a = check_args(Xs, XsT, GT, W, partial, y);
-    TORCH_CHECK(batch_size % 128 == 0, "batch_size must be a mult of 128");
+    auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+                                col_class, col_fold, col_class2, col_lr,
+                                col_l2, fmask, row_w, batch_size, momentum,
+                                intercept_row);
+    check_batches(a, batch_size, inv_m_cpu);
     const float* inv_p = (const float*)inv_m_cpu.data_ptr();
     auto torch_stream = c10::hip::getCurrentHIPStream().stream();
     auto body = [&](hipStream_t st) {
@@ -301,11 +397,11 @@ void sgd_epoch_l1(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                   int64_t loss_id, double lr_scale, double momentum,
                   int64_t intercept_row, torch::Tensor col_l1,
                   torch::Tensor cpos, torch::Tensor cneg) {
-    auto a = check_args(Xs, XsT, GT, W, partial, y);
-    TORCH_CHECK(batch_size % 128 == 0, "batch_size must be a mult of 128");
-    TORCH_CHECK(!inv_m_cpu.is_cuda(), "inv_m must be a CPU tensor");
-    TORCH_CHECK(inv_m_cpu.numel() >= n_batches_of(a, batch_size),
-                "inv_m shorter than the batch count");
+    auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+                                col_class, col_fold, col_class2, col_lr,
+                                col_l2, fmask, row_w, batch_size, momentum,
+                                intercept_row);
+    check_batches(a, batch_size, inv_m_cpu);
     auto l1 = check_l1(col_l1, cpos, cneg, W, momentum);
     enqueue_epoch(a, Xs, XsT, GT, W, V, WbfT, partial, y, fold, col_class,
                   col_fold, col_class2, col_lr, col_l2, fmask, row_w,
@@ -325,11 +421,11 @@ void sgd_solve_l1(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                   int64_t loss_id, double momentum, int64_t intercept_row,
                   int64_t epochs, torch::Tensor col_l1, torch::Tensor cpos,
                   torch::Tensor cneg) {
-    auto a = check_args(Xs, XsT, GT, W, partial, y);
-    TORCH_CHECK(batch_size % 128 == 0, "batch_size must be a mult of 128");
-    TORCH_CHECK(!inv_m_cpu.is_cuda(), "inv_m must be a CPU tensor");
-    TORCH_CHECK(inv_m_cpu.numel() >= n_batches_of(a, batch_size),
-                "inv_m shorter than the batch count");
+    auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+                                col_class, col_fold, col_class2, col_lr,
+                                col_l2, fmask, row_w, batch_size, momentum,
+                                intercept_row);
+    check_batches(a, batch_size, inv_m_cpu);
     auto l1 = check_l1(col_l1, cpos, cneg, W, momentum);
     const float* inv_p = (const float*)inv_m_cpu.data_ptr();
     auto torch_stream = c10::hip::getCurrentHIPStream().stream();
@@ -685,29 +781,6 @@ extern "C" hipError_t skdist_hash_vectorize_utf8(
 
 namespace {
 
-// ---- argument checks of the tree bindings.  The launchers take void*, so
-// every tensor that reaches one is first pinned to the device, layout and
-// dtype its kernel reads; a binding launches nothing on empty work.
-void check_t(const torch::Tensor& t, torch::ScalarType dt,
-             const char* name) {
-    TORCH_CHECK(t.is_cuda(), name, " must be on the GPU");
-    TORCH_CHECK(t.is_contiguous(), name, " not contiguous");
-    TORCH_CHECK(t.scalar_type() == dt, name, " must be ", dt);
-}
-
-void check_vec(const torch::Tensor& t, torch::ScalarType dt, int64_t len,
-               const char* name) {
-    check_t(t, dt, name);
-    TORCH_CHECK(t.numel() == len, name, " must have ", len, " elements");
-}
-
-void check_2d(const torch::Tensor& t, torch::ScalarType dt, int64_t rows,
-              int64_t cols, const char* name) {
-    check_t(t, dt, name);
-    TORCH_CHECK(t.dim() == 2 && t.size(0) == rows && t.size(1) == cols,
-                name, " must be [", rows, ", ", cols, "]");
-}
-
 // codes [n, fp] u8 with fp a multiple of 4 (uchar4 loads); returns fp
 int64_t check_codes(const torch::Tensor& codes, int64_t n) {
     check_t(codes, torch::kUInt8, "codes");
@@ -1044,34 +1117,46 @@ void bin_csr(torch::Tensor indptr, torch::Tensor indices,
         "bin_csr");
 }
 
+// stats: [ncols_pad * 2] (mode 0: hits, rows) or [ncols_pad] (mode 1: sse),
+// zeroed by the caller; the kernel adds into it
 void score_fold(torch::Tensor Xf, torch::Tensor WbfT, torch::Tensor yf,
                 torch::Tensor out, int64_t mode) {
-    for (auto* t : {&Xf, &WbfT, &yf, &out}) {
-        CHECK_DEV(*t);
-        CHECK_CONT(*t);
-    }
-    TORCH_CHECK(Xf.scalar_type() == torch::kBFloat16, "Xf must be bf16");
-    TORCH_CHECK(Xf.size(0) % 128 == 0, "m_pad must be a mult of 128");
-    TORCH_CHECK(WbfT.size(0) % 128 == 0, "ncols_pad mult of 128");
+    TORCH_CHECK(mode == 0 || mode == 1, "mode must be 0 or 1");
+    check_t(Xf, torch::kBFloat16, "Xf");
+    TORCH_CHECK(Xf.dim() == 2 && Xf.size(0) >= 128 &&
+                Xf.size(0) % 128 == 0, "m_pad must be a mult of 128");
+    const int64_t m_pad = Xf.size(0), fa = Xf.size(1);
+    TORCH_CHECK(fa >= 32 && fa % 32 == 0, "fa must be a multiple of 32");
+    check_t(WbfT, torch::kBFloat16, "WbfT");
+    TORCH_CHECK(WbfT.dim() == 2 && WbfT.size(1) == fa &&
+                WbfT.size(0) >= 128 && WbfT.size(0) % 128 == 0,
+                "WbfT must be [ncols_pad, fa], ncols_pad a mult of 128");
+    const int64_t ncols_pad = WbfT.size(0);
+    check_vec(yf, torch::kFloat32, m_pad, "yf");
+    check_vec(out, torch::kFloat32, ncols_pad * (mode == 0 ? 2 : 1),
+              "stats");
     auto stream = c10::hip::getCurrentHIPStream().stream();
     hipError_t err = skdist_score(
         Xf.data_ptr(), WbfT.data_ptr(), yf.data_ptr(), out.data_ptr(),
-        Xf.size(0), (int)Xf.size(1), (int)WbfT.size(0), (int)mode,
-        stream);
+        m_pad, (int)fa, (int)ncols_pad, (int)mode, stream);
     TORCH_CHECK(err == hipSuccess, "score_fold: ", hipGetErrorString(err));
 }
 
 void standardize(torch::Tensor X, torch::Tensor mean,
                  torch::Tensor inv_std, torch::Tensor out, int64_t f) {
-    for (auto* t : {&X, &mean, &inv_std, &out}) {
-        CHECK_DEV(*t);
-        CHECK_CONT(*t);
-    }
-    TORCH_CHECK(out.scalar_type() == torch::kBFloat16, "out must be bf16");
+    check_t(out, torch::kBFloat16, "out");
+    TORCH_CHECK(out.dim() == 2, "out must be [n, fa]");
+    const int64_t n = out.size(0), fa = out.size(1);
+    TORCH_CHECK(fa % 8 == 0, "fa must be a multiple of 8");
+    TORCH_CHECK(f >= 1 && f < fa, "f must be in [1, fa)");
+    check_2d(X, torch::kFloat32, n, f, "X");
+    check_vec(mean, torch::kFloat32, f, "mean");
+    check_vec(inv_std, torch::kFloat32, f, "inv_std");
+    if (n == 0) return;
     auto stream = c10::hip::getCurrentHIPStream().stream();
     hipError_t err = skdist_standardize(
         X.data_ptr(), mean.data_ptr(), inv_std.data_ptr(), out.data_ptr(),
-        out.size(0), (int)f, (int)out.size(1), stream);
+        n, (int)f, (int)fa, stream);
     TORCH_CHECK(err == hipSuccess, "standardize: ",
                 hipGetErrorString(err));
 }

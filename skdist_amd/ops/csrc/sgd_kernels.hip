@@ -536,22 +536,23 @@ extern "C" hipError_t skdist_standardize(
 // needed: every row scores every column.
 //   mode 0 (binary accuracy): out[col*2]   += #(sign(z) == y)
 //                             out[col*2+1] += #rows           (valid)
-//   mode 1 (regression):      out[col*3]   += (z-y)^2
-//                             out[col*3+1] += y, out[col*3+2] += y^2
+//   mode 1 (regression):      out[col]     += (z-y)^2
+// (r2's total sum of squares depends on y alone, not on the column: the
+// caller takes it from the fold's y in float64, _sgd._score_fold_hip)
 // grid: (m_pad/128, ncols_pad/128), block 256 (4 waves of 64x64).
 // ---------------------------------------------------------------------- //
 extern "C" __global__ __launch_bounds__(256) void k_score(
     const __bf16* __restrict__ Xf,    // [m_pad][fa] gathered fold rows
     const __bf16* __restrict__ WbfT,  // [ncols_pad][fa]
     const float* __restrict__ yf,     // [m_pad] (-1e30 pad sentinel)
-    float* __restrict__ out,          // [ncols_pad * (2|3)]
+    float* __restrict__ out,          // [ncols_pad * (2|1)]
     int fa, int ncols_pad, int mode)
 {
     extern __shared__ __attribute__((aligned(16))) char sm[];
     #define sbufA(b) ((__bf16*)(sm + (b) * 16384))
     #define sbufB(b) ((__bf16*)(sm + 8192 + (b) * 16384))
     float* y_s = (float*)(sm + 32768);        // [128]
-    float* red = (float*)(sm + 33280);        // [3][132] per-col partials
+    float* red = (float*)(sm + 33280);        // [132] per-col partials
 
     const int tid = threadIdx.x;
     const int bm = blockIdx.x * 128;
@@ -621,7 +622,7 @@ extern "C" __global__ __launch_bounds__(256) void k_score(
 
     // per-lane partials over this wave's 16 rows x 4 col-groups
     const int rw = lane >> 4;
-    float s0[4] = {}, s1[4] = {}, s2[4] = {};
+    float s0[4] = {}, s1[4] = {};
     #pragma unroll
     for (int mi = 0; mi < 4; ++mi) {
         #pragma unroll
@@ -638,23 +639,20 @@ extern "C" __global__ __launch_bounds__(256) void k_score(
                 } else {
                     const float e = z - yv;
                     s0[ni] += e * e;
-                    s1[ni] += yv;
-                    s2[ni] += yv * yv;
                 }
             }
         }
     }
     // reduce across the 16 lanes-groups sharing a column (rows axis):
     // lanes with same (lane&15, wc) hold different rows; use LDS.
-    const int nstat = (mode == 0) ? 2 : 3;
+    const int nstat = (mode == 0) ? 2 : 1;
     for (int st = 0; st < nstat; ++st) {
         __syncthreads();
         for (int i = tid; i < 132; i += 256) red[i] = 0.f;
         __syncthreads();
         #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
-            const float v = (st == 0) ? s0[ni] : (st == 1 ? s1[ni]
-                                                          : s2[ni]);
+            const float v = (st == 0) ? s0[ni] : s1[ni];
             atomicAdd(&red[wc + ni * 16 + fr], v);
         }
         __syncthreads();

@@ -48,7 +48,12 @@ _CRITERIA = {
     "mse": CRIT_MSE,
 }
 
-MAX_DEVICE_CLASSES = 32
+# widest class-count vector the tree kernels take (tree_kernels.hip WIDE_S,
+# predict_kernels.hip MAXVS_WIDE); up to NARROW_STATS the thread-per-feature
+# / thread-per-row kernels run, above it the wave-per-feature / wave-per-row
+# ones
+MAX_DEVICE_CLASSES = 256
+NARROW_STATS = 32
 _U32 = np.uint32
 
 
@@ -611,6 +616,21 @@ class _NodeStore:
         return out
 
 
+def hist_groups(f, nbins, S, budget):
+    """(fg, cg) of the class-grouped histogram kernel: features and
+    classes per LDS tile with ``fg * nbins * cg * 4 <= budget`` bytes.
+
+    The classes are cut first, and only as far as it takes to keep four
+    features (one uchar4 code load) in a tile where the data has four:
+    every class group scans the node's rows again, while a narrow feature
+    group loses the vector load.  What is left of the budget then widens
+    the feature group, in steps of four."""
+    cells = budget // (nbins * 4)              # (feature, class) pairs
+    cg = min(S, max(1, cells // min(f, 4)))
+    fg = max(1, min(f, cells // cg))
+    return (fg // 4 * 4 if fg >= 4 else fg), cg
+
+
 class ForestBuilder:
     """Grows a batch of trees level-by-level against one BinnedDataset.
 
@@ -662,10 +682,17 @@ class ForestBuilder:
         self._w_scale = 1.0
         self._mss_eff = self.mss
         self._msl_eff = self.msl
-        # features per LDS group for the hist kernel
-        per_feat = ds.nbins * ds.S * 4
-        fg = max(1, min(ds.f, self.LDS_BUDGET_BYTES // per_feat))
-        self.fg = fg // 4 * 4 if fg >= 4 else fg
+        # features per LDS group for the hist kernel; above NARROW_STATS
+        # classes also the classes per group (hist_groups), None = one
+        # tile over all S stats
+        self.cg = None
+        if ds.is_cls and ds.S > NARROW_STATS:
+            self.fg, self.cg = hist_groups(ds.f, ds.nbins, ds.S,
+                                           self.LDS_BUDGET_BYTES)
+        else:
+            per_feat = ds.nbins * ds.S * 4
+            fg = max(1, min(ds.f, self.LDS_BUDGET_BYTES // per_feat))
+            self.fg = fg // 4 * 4 if fg >= 4 else fg
 
     # -------------------------------------------------------------- #
     def build(self, seeds, sample_weight=None):
@@ -1045,7 +1072,8 @@ class ForestBuilder:
             ds.codes, ds.y_int if ds.is_cls else absent,
             absent if ds.is_cls else ds.y_f,
             absent if ds.row_w is None else ds.row_w,
-            weights, si, chunks, hist, ds.n, ds.f, ds.nbins, self.fg)
+            weights, si, chunks, hist, ds.n, ds.f, ds.nbins, self.fg,
+            *(() if self.cg is None else (self.cg,)))
 
     def _run_split_kernel(self, hist, node_seed, NF):
         ds = self.ds
@@ -1621,17 +1649,20 @@ def flat_forest_for(model, device):
         return None  # (a boosted model's [n_stages, K] array is not a
         # flat forest — those models expose _device_predict_fn instead)
     trees = list(trees)
-    # the traversal kernel carries <=32 payload values per leaf
-    # (predict_kernels.hip MAXVS); wider-class forests score on the
-    # host path instead of erroring at launch
+    # the traversal kernels carry <= MAX_DEVICE_CLASSES payload values per
+    # leaf (predict_kernels.hip MAXVS_WIDE); wider-class forests score on
+    # the host path instead of erroring at launch.  So do the forests
+    # above NARROW_STATS classes when the device is not a GPU.
+    widest = (MAX_DEVICE_CLASSES if torch.device(device).type == "cuda"
+              else NARROW_STATS)
     if all(isinstance(t, HistTree) for t in trees):
-        if trees[0].value.shape[1] > 32:
+        if trees[0].value.shape[1] > widest:
             return None
         return FlatForest(trees, device)
     if all(hasattr(t, "tree_") for t in trees):
         is_cls = hasattr(trees[0], "predict_proba") and hasattr(
             model, "classes_")
-        if is_cls and len(model.classes_) > 32:
+        if is_cls and len(model.classes_) > widest:
             return None
         flat = FlatForest(
             [

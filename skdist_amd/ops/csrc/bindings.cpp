@@ -838,8 +838,8 @@ int64_t check_payload(const torch::Tensor& values, const torch::Tensor& out,
                       int64_t rows) {
     check_t(values, torch::kFloat32, "values");
     TORCH_CHECK(values.dim() == 2 && values.size(1) >= 1 &&
-                    values.size(1) <= 32,
-                "values must be [n_values, vs] with vs <= 32 (MAXVS)");
+                    values.size(1) <= 256,
+                "values must be [n_values, vs] with vs <= 256 (MAXVS_WIDE)");
     check_2d(out, torch::kFloat32, rows, values.size(1), "out");
     return values.size(1);
 }
@@ -872,7 +872,7 @@ void tree_hist(torch::Tensor codes, torch::Tensor y_int, torch::Tensor y_f,
                torch::Tensor row_w, torch::Tensor weights,
                torch::Tensor sample_idx, torch::Tensor chunks,
                torch::Tensor hist, int64_t n, int64_t f, int64_t nbins,
-               int64_t fg) {
+               int64_t fg, int64_t cg) {
     const int64_t fp = check_codes(codes, n);
     const int64_t n_chunks = check_chunks(chunks);
     const int64_t TB = check_plane(weights, torch::kUInt8, n, "weights");
@@ -898,15 +898,30 @@ void tree_hist(torch::Tensor codes, torch::Tensor y_int, torch::Tensor y_f,
                     "hist must be [NF, f, nbins, 4] with row_w and "
                     "[NF, f, nbins, 3] without");
     }
-    TORCH_CHECK(fg >= 1 && fg <= fp && fg * nbins * S * 4 <= 64 * 1024,
-                "fg * nbins * S * 4 bytes must fit 64 KiB of LDS");
+    // cg = -1 (the default): not grouped; else the class-group width
+    const bool grouped = cg != -1;
+    if (grouped) {
+        TORCH_CHECK(cg > 0, "cg must be > 0 (leave it out for one tile "
+                            "over all S stats)");
+        TORCH_CHECK(cls && !has_w,
+                    "class groups (cg) split class counts only: y_int and "
+                    "no row_w");
+    }
+    const int64_t tile_s = grouped && cg < S ? cg : S;
+    TORCH_CHECK(fg >= 1 && fg <= fp && fg * nbins * tile_s * 4 <= 64 * 1024,
+                grouped ? "fg * nbins * min(cg, S) * 4 bytes must fit 64 "
+                          "KiB of LDS"
+                        : "fg * nbins * S * 4 bytes must fit 64 KiB of LDS");
+    TORCH_CHECK(!grouped || (S + cg - 1) / cg <= 65535,
+                "too many class groups");
     if (n_chunks == 0) return;
     launched(skdist_tree_hist(
         codes.data_ptr(), cls ? y_int.data_ptr() : nullptr,
         cls ? nullptr : y_f.data_ptr(),
         has_w ? row_w.data_ptr() : nullptr, weights.data_ptr(),
         sample_idx.data_ptr(), chunks.data_ptr(), hist.data_ptr(), n,
-        (int)f, (int)fp, (int)nbins, (int)S, (int)fg, (int)n_chunks,
+        (int)f, (int)fp, (int)nbins, (int)S, (int)fg,
+        grouped ? (int)std::min<int64_t>(cg, S) : 0, (int)n_chunks,
         cur_stream()), "tree_hist");
 }
 
@@ -931,9 +946,15 @@ void tree_split(torch::Tensor hist, torch::Tensor node_seed, int64_t f,
     check_vec(out_imp, torch::kFloat32, NF, "out_imp");
     check_vec(out_stats, torch::kFloat32, NF * S, "out_stats");
     check_vec(out_lstats, torch::kFloat32, NF * S, "out_lstats");
-    TORCH_CHECK(S >= 1 && S <= 32, "tree_split supports <= 32 stats");
+    TORCH_CHECK(S >= 1 && S <= 256, "tree_split supports <= 256 stats");
     TORCH_CHECK(cnt_stat >= -1 && cnt_stat < S,
                 "cnt_stat must be -1 or a stat index");
+    TORCH_CHECK(S <= 32 || is_cls != 0,
+                "tree_split: more than 32 stats are class counts only "
+                "(is_cls = 1)");
+    TORCH_CHECK(S <= 32 || cnt_stat == -1,
+                "tree_split: more than 32 stats have no counted variant "
+                "(cnt_stat must be -1)");
     TORCH_CHECK(f >= 1 && nbins >= 1 && NF < (1LL << 31) &&
                     hist.numel() >= NF * f * nbins * S, "hist too small");
     TORCH_CHECK(missing == 0 || missing == 1, "missing must be 0 or 1");
@@ -1254,12 +1275,18 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "tokenize + murmur3 feature hashing -> COO pairs");
     m.def("hash_vectorize_utf8", &hash_vectorize_utf8,
           "UTF-8 tokenize + murmur3 feature hashing -> COO pairs");
+    // the trailing arguments with defaults are the class-group width and
+    // the missing-value ones; every entry keeps its earlier positional
+    // argument list
+    namespace py = pybind11;
     m.def("tree_hist", &tree_hist,
           "per-(node,feature,bin) stats: class counts, (w,wy,wyy), or "
-          "(W,Wy,Wyy,C) with f32 row weights");
-    // the trailing arguments with defaults are the missing-value ones;
-    // every entry keeps its earlier positional argument list
-    namespace py = pybind11;
+          "(W,Wy,Wyy,C) with f32 row weights; cg > 0 splits the class "
+          "counts into class groups of cg, one LDS tile each",
+          py::arg("codes"), py::arg("y_int"), py::arg("y_f"),
+          py::arg("row_w"), py::arg("weights"), py::arg("sample_idx"),
+          py::arg("chunks"), py::arg("hist"), py::arg("n"), py::arg("f"),
+          py::arg("nbins"), py::arg("fg"), py::arg("cg") = -1);
     m.def("tree_split", &tree_split,
           "best split per frontier node; min-leaf on the weight sums "
           "(cnt_stat = -1) or on a count stat; missing = 1 scans both "

@@ -6,12 +6,16 @@
 // table resident in HBM (small enough to sit in L2/L3), and every thread
 // walks all trees for one row, accumulating leaf payloads in registers.
 //
-// There is ONE walk (descend) and ONE predict / apply body, templated on a
-// row accessor with a single `float at(int jf)` and on a bool MISS (NaN
-// follows a per-node direction flag); the eight kernels are predict/apply
-// x dense/CSR x MISS instantiations of them.  One thread per row and
-// trees in order t = 0..T-1, so the accumulation order — and therefore
-// every output bit — is the same for a CSR row and for its dense copy.
+// There is ONE walk (descend) and ONE apply body, templated on a row
+// accessor with a single `float at(int jf)` and on a bool MISS (NaN
+// follows a per-node direction flag), and two predict bodies by payload
+// width: predict_row (vs <= 32, one thread per row, the payload in
+// registers) and predict_row_wide (32 < vs <= 256, one wave per row, the
+// payload across the lanes).  The twelve kernels are {predict, predict
+// wide, apply} x dense/CSR x MISS instantiations of them.  Trees go in
+// order t = 0..T-1 in every body, so the accumulation order — and
+// therefore every output bit — is the same for a CSR row and for its
+// dense copy.
 //
 // Layouts:
 //   X       [rows][f]  f32 row-major
@@ -29,7 +33,9 @@
 #include "common.h"
 #include "tree_api.h"
 
-#define MAXVS 32
+#define MAXVS 32        // widest payload of the thread-per-row predict
+#define MAXVS_WIDE 256  // widest payload of the wave-per-row predict
+#define WAVE 64
 
 struct DenseRow {
     const float* __restrict__ x;
@@ -118,6 +124,36 @@ static __device__ __forceinline__ void predict_row(
         if (c < vs) out[r * vs + c] = acc[c] * inv;
 }
 
+// predict_row for MAXVS < vs <= MAXVS_WIDE, called by a whole wave for ONE
+// row: all 64 lanes walk the same root-to-leaf path (uniform control flow,
+// every node load a broadcast), then lane l adds the leaf's payload values
+// l, l+64, l+128, l+192 — coalesced along vs, at most 4 accumulators.
+template <bool MISS, typename Row>
+static __device__ __forceinline__ void predict_row_wide(
+    const Row& row, const int* __restrict__ feat,
+    const float* __restrict__ thr, const int* __restrict__ left,
+    const int* __restrict__ right, const int* __restrict__ roots,
+    const float* __restrict__ values,
+    const unsigned char* __restrict__ mleft, float* __restrict__ out,
+    long long r, int n_trees, int vs) {
+    const int lane = threadIdx.x & (WAVE - 1);
+    float acc[MAXVS_WIDE / WAVE];
+#pragma unroll
+    for (int k = 0; k < MAXVS_WIDE / WAVE; ++k) acc[k] = 0.f;
+    for (int t = 0; t < n_trees; ++t) {
+        const int node =
+            descend<MISS>(row, feat, thr, left, right, roots, mleft, t);
+        const float* v = values + (long long)left[node] * vs;
+#pragma unroll
+        for (int k = 0; k < MAXVS_WIDE / WAVE; ++k)
+            if (lane + k * WAVE < vs) acc[k] += v[lane + k * WAVE];
+    }
+    const float inv = 1.f / (float)n_trees;
+#pragma unroll
+    for (int k = 0; k < MAXVS_WIDE / WAVE; ++k)
+        if (lane + k * WAVE < vs) out[r * vs + lane + k * WAVE] = acc[k] * inv;
+}
+
 // leaf node id per tree -> out_leaf[r][0..n_trees)
 template <bool MISS, typename Row>
 static __device__ __forceinline__ void apply_row(
@@ -131,9 +167,15 @@ static __device__ __forceinline__ void apply_row(
             descend<MISS>(row, feat, thr, left, right, roots, mleft, t);
 }
 
-// The eight kernels: {predict, apply} x {dense, CSR} x {plain, _m}.  The
-// plain ones are the MISS = false instantiations and take no mleft.
-#define FOREST_PREDICT_KERNEL(NAME, MISS, MLEFT_PARAM, MLEFT)               \
+// The twelve kernels: {predict, predict wide, apply} x {dense, CSR} x
+// {plain, _m}.  The plain ones are the MISS = false instantiations and take
+// no mleft.  ROW is the row a thread works on: its own (THREAD_ROW), or its
+// wave's with 4 rows per 256-thread block (WAVE_ROW, the wide body).
+#define THREAD_ROW ((long long)blockIdx.x * blockDim.x + threadIdx.x)
+#define WAVE_ROW                                                            \
+    ((long long)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE)
+
+#define FOREST_PREDICT_KERNEL(NAME, BODY, ROW, MISS, MLEFT_PARAM, MLEFT)    \
     extern "C" __global__ __launch_bounds__(256) void NAME(                 \
         const float* __restrict__ X, const int* __restrict__ feat,          \
         const float* __restrict__ thr, const int* __restrict__ left,        \
@@ -141,11 +183,10 @@ static __device__ __forceinline__ void apply_row(
         const float* __restrict__ values, MLEFT_PARAM                       \
         float* __restrict__ out, long long rows, int f, int n_trees,        \
         int vs) {                                                           \
-        const long long r =                                                 \
-            (long long)blockIdx.x * blockDim.x + threadIdx.x;               \
+        const long long r = ROW;                                            \
         if (r >= rows) return;                                              \
-        predict_row<MISS>(DenseRow(X, r, f), feat, thr, left, right, roots, \
-                          values, MLEFT, out, r, n_trees, vs);              \
+        BODY<MISS>(DenseRow(X, r, f), feat, thr, left, right, roots,        \
+                   values, MLEFT, out, r, n_trees, vs);                     \
     }
 
 #define FOREST_APPLY_KERNEL(NAME, MISS, MLEFT_PARAM, MLEFT)                 \
@@ -162,7 +203,8 @@ static __device__ __forceinline__ void apply_row(
                         MLEFT, out_leaf, r, n_trees);                       \
     }
 
-#define FOREST_PREDICT_CSR_KERNEL(NAME, MISS, MLEFT_PARAM, MLEFT)           \
+#define FOREST_PREDICT_CSR_KERNEL(NAME, BODY, ROW, MISS, MLEFT_PARAM,       \
+                                  MLEFT)                                    \
     extern "C" __global__ __launch_bounds__(256) void NAME(                 \
         const long long* __restrict__ indptr,                               \
         const int* __restrict__ indices, const float* __restrict__ data,    \
@@ -171,12 +213,10 @@ static __device__ __forceinline__ void apply_row(
         const int* __restrict__ roots, const float* __restrict__ values,    \
         MLEFT_PARAM float* __restrict__ out, long long rows,                \
         long long nnz, int n_trees, int vs) {                               \
-        const long long r =                                                 \
-            (long long)blockIdx.x * blockDim.x + threadIdx.x;               \
+        const long long r = ROW;                                            \
         if (r >= rows) return;                                              \
-        predict_row<MISS>(CsrRow(indptr, indices, data, r, nnz), feat, thr, \
-                          left, right, roots, values, MLEFT, out, r,        \
-                          n_trees, vs);                                     \
+        BODY<MISS>(CsrRow(indptr, indices, data, r, nnz), feat, thr, left,  \
+                   right, roots, values, MLEFT, out, r, n_trees, vs);       \
     }
 
 #define FOREST_APPLY_CSR_KERNEL(NAME, MISS, MLEFT_PARAM, MLEFT)             \
@@ -197,22 +237,40 @@ static __device__ __forceinline__ void apply_row(
 
 #define NO_MLEFT_PARAM
 #define MLEFT_PARAM_ const unsigned char* __restrict__ mleft,
-FOREST_PREDICT_KERNEL(k_forest_predict, false, NO_MLEFT_PARAM, nullptr)
-FOREST_PREDICT_KERNEL(k_forest_predict_m, true, MLEFT_PARAM_, mleft)
+FOREST_PREDICT_KERNEL(k_forest_predict, predict_row, THREAD_ROW, false,
+                      NO_MLEFT_PARAM, nullptr)
+FOREST_PREDICT_KERNEL(k_forest_predict_m, predict_row, THREAD_ROW, true,
+                      MLEFT_PARAM_, mleft)
+FOREST_PREDICT_KERNEL(k_forest_predict_wide, predict_row_wide, WAVE_ROW,
+                      false, NO_MLEFT_PARAM, nullptr)
+FOREST_PREDICT_KERNEL(k_forest_predict_wide_m, predict_row_wide, WAVE_ROW,
+                      true, MLEFT_PARAM_, mleft)
 FOREST_APPLY_KERNEL(k_forest_apply, false, NO_MLEFT_PARAM, nullptr)
 FOREST_APPLY_KERNEL(k_forest_apply_m, true, MLEFT_PARAM_, mleft)
-FOREST_PREDICT_CSR_KERNEL(k_forest_predict_csr, false, NO_MLEFT_PARAM,
-                          nullptr)
-FOREST_PREDICT_CSR_KERNEL(k_forest_predict_csr_m, true, MLEFT_PARAM_, mleft)
+FOREST_PREDICT_CSR_KERNEL(k_forest_predict_csr, predict_row, THREAD_ROW,
+                          false, NO_MLEFT_PARAM, nullptr)
+FOREST_PREDICT_CSR_KERNEL(k_forest_predict_csr_m, predict_row, THREAD_ROW,
+                          true, MLEFT_PARAM_, mleft)
+FOREST_PREDICT_CSR_KERNEL(k_forest_predict_csr_wide, predict_row_wide,
+                          WAVE_ROW, false, NO_MLEFT_PARAM, nullptr)
+FOREST_PREDICT_CSR_KERNEL(k_forest_predict_csr_wide_m, predict_row_wide,
+                          WAVE_ROW, true, MLEFT_PARAM_, mleft)
 FOREST_APPLY_CSR_KERNEL(k_forest_apply_csr, false, NO_MLEFT_PARAM, nullptr)
 FOREST_APPLY_CSR_KERNEL(k_forest_apply_csr_m, true, MLEFT_PARAM_, mleft)
 
 // ---------------------------------------------------------------------- //
-// C launchers: one thread per row, block 256; mleft != nullptr picks the
-// MISS instantiation
+// C launchers: block 256, one thread per row (predict with vs <= MAXVS,
+// apply) or one wave per row (predict with MAXVS < vs <= MAXVS_WIDE);
+// mleft != nullptr picks the MISS instantiation
 // ---------------------------------------------------------------------- //
 static inline dim3 row_grid(long long rows) {
     return dim3((unsigned)((rows + 255) / 256));
+}
+// rows_per_block = 256 / WAVE; false where the grid would pass 2^31 - 1
+static inline bool wave_grid(long long rows, dim3* grid) {
+    const long long blocks = (rows + 256 / WAVE - 1) / (256 / WAVE);
+    *grid = dim3((unsigned)blocks);
+    return blocks <= 0x7fffffffLL;
 }
 
 extern "C" hipError_t skdist_forest_predict(
@@ -220,8 +278,28 @@ extern "C" hipError_t skdist_forest_predict(
     const void* right, const void* roots, const void* values,
     const void* mleft, void* out, long long rows, int f, int n_trees,
     int vs, hipStream_t stream) {
-    if (vs > MAXVS) return hipErrorInvalidValue;
+    if (vs <= 0 || vs > MAXVS_WIDE) return hipErrorInvalidValue;
     if (rows <= 0) return hipSuccess;
+    if (vs > MAXVS) {
+        dim3 grid;
+        if (!wave_grid(rows, &grid)) return hipErrorInvalidValue;
+        if (mleft != nullptr)
+            hipLaunchKernelGGL(k_forest_predict_wide_m, grid, dim3(256), 0,
+                               stream, (const float*)X, (const int*)feat,
+                               (const float*)thr, (const int*)left,
+                               (const int*)right, (const int*)roots,
+                               (const float*)values,
+                               (const unsigned char*)mleft, (float*)out,
+                               rows, f, n_trees, vs);
+        else
+            hipLaunchKernelGGL(k_forest_predict_wide, grid, dim3(256), 0,
+                               stream, (const float*)X, (const int*)feat,
+                               (const float*)thr, (const int*)left,
+                               (const int*)right, (const int*)roots,
+                               (const float*)values, (float*)out, rows, f,
+                               n_trees, vs);
+        return hipGetLastError();
+    }
     if (mleft != nullptr)
         hipLaunchKernelGGL(k_forest_predict_m, row_grid(rows), dim3(256), 0,
                            stream, (const float*)X, (const int*)feat,
@@ -268,8 +346,30 @@ extern "C" hipError_t skdist_forest_predict_csr(
     const void* roots, const void* values, const void* mleft, void* out,
     long long rows, long long nnz, int n_trees, int vs,
     hipStream_t stream) {
-    if (vs > MAXVS) return hipErrorInvalidValue;
+    if (vs <= 0 || vs > MAXVS_WIDE) return hipErrorInvalidValue;
     if (rows <= 0) return hipSuccess;
+    if (vs > MAXVS) {
+        dim3 grid;
+        if (!wave_grid(rows, &grid)) return hipErrorInvalidValue;
+        if (mleft != nullptr)
+            hipLaunchKernelGGL(k_forest_predict_csr_wide_m, grid, dim3(256),
+                               0, stream, (const long long*)indptr,
+                               (const int*)indices, (const float*)data,
+                               (const int*)feat, (const float*)thr,
+                               (const int*)left, (const int*)right,
+                               (const int*)roots, (const float*)values,
+                               (const unsigned char*)mleft, (float*)out,
+                               rows, nnz, n_trees, vs);
+        else
+            hipLaunchKernelGGL(k_forest_predict_csr_wide, grid, dim3(256),
+                               0, stream, (const long long*)indptr,
+                               (const int*)indices, (const float*)data,
+                               (const int*)feat, (const float*)thr,
+                               (const int*)left, (const int*)right,
+                               (const int*)roots, (const float*)values,
+                               (float*)out, rows, nnz, n_trees, vs);
+        return hipGetLastError();
+    }
     if (mleft != nullptr)
         hipLaunchKernelGGL(k_forest_predict_csr_m, row_grid(rows),
                            dim3(256), 0, stream, (const long long*)indptr,

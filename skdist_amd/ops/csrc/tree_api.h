@@ -7,13 +7,18 @@
 
 extern "C" {
 // row_w == nullptr: class counts (y_int) or (w, wy, wyy) (y_f);
-// row_w != nullptr: (W, Wy, Wyy, C) over y_f, S must be 4
+// row_w != nullptr: (W, Wy, Wyy, C) over y_f, S must be 4.
+// cg == 0: one LDS tile of fg * nbins * S floats per block; cg > 0 (class
+// counts only): the classes go in groups of cg over grid.z and the tile is
+// fg * nbins * min(cg, S) floats.  The tile must fit 64 KiB either way
 hipError_t skdist_tree_hist(
     const void* codes, const void* y_int, const void* y_f,
     const void* row_w, const void* weights, const void* sample_idx,
     const void* chunks, void* hist, long long n, int f, int fp, int nbins,
-    int S, int fg, int n_chunks, hipStream_t stream);
+    int S, int fg, int cg, int n_chunks, hipStream_t stream);
 // cnt_stat < 0: min-leaf on the weight sums; else on the stat cnt_stat.
+// S <= 32: any stats; 32 < S <= 256: class counts only (is_cls, cnt_stat
+// < 0), scanned by the wave-per-feature kernels.
 // missing != 0: bin nbins-1 is the missing bin, both directions are
 // scanned and out_mleft [n_frontier] int32 gets the learned one (no
 // extra_mode); missing == 0: out_mleft is not touched and may be null

@@ -9,18 +9,24 @@
 //   K1 k_tree_hist:    per-(node,feature,bin) weighted stats, LDS-staged
 //      k_tree_hist_w:  the regression stats with a real-valued f32 row-weight
 //                      plane on top of the uint8 one, plus a row-count slot
+//      k_tree_hist_cg: class counts with the classes split into groups of
+//                      cg, one LDS tile per (feature group, class group)
 //   K2 k_tree_split:   best (feature,bin) per frontier node — gini /
 //                      entropy / mse scan with exact max_features
 //                      subsampling and ExtraTrees random-threshold mode
 //      k_tree_split_w: same scan; the min-leaf test reads a count slot
+//      k_tree_split_wide: the classification scan for 32 < S <= 256, one
+//                      wave per feature with the classes across its lanes
 //   K3 k_part_count:   per-chunk left-row counts for the stable partition
 //   K4 k_part_scatter: stable partition of each node's sample segment
 //
-// K1 and K2 have ONE body each (tree_hist_body<ROW_W>,
-// tree_split_body<COUNTED, MISSING>) behind the kernel names, and ONE
-// checked launcher each (tree_api.h) that picks the instantiation:
-// skdist_tree_hist by row_w != nullptr, skdist_tree_split by cnt_stat >= 0
-// and by its `missing` flag.
+// K1 has ONE body (tree_hist_body<ROW_W, GROUPED>); K2 has one per register
+// layout (tree_split_body<COUNTED, MISSING>: a thread per feature, S <= 32;
+// tree_split_wide_body<MISSING>: a wave per feature, S <= 256) that share
+// the feature subsample and the block-level ending.  ONE checked launcher
+// each (tree_api.h) picks the instantiation: skdist_tree_hist by
+// row_w != nullptr and cg > 0, skdist_tree_split by S > 32, cnt_stat >= 0
+// and its `missing` flag.
 //
 // Missing values: a dataset binned with a missing bin keeps code nbins-1
 // for NaN cells.  K1 is unchanged (missing is one more bin); the MISSING
@@ -40,6 +46,10 @@
 //   hist       [NF][f][nbins][S] f32   S = n_classes (cls) | 3 (w,wy,wyy)
 //                                       | 4 (W,Wy,Wyy,C) with row_w, where
 //                                       w = weights*row_w and C = Σ weights
+//   hist LDS   [fg][nbins][S] f32      one tile per (chunk, feature group);
+//              [fg][nbins][cg]         class-grouped: per (chunk, feature
+//                                      group, class group), the block of
+//                                      group z owning classes [z*cg, z*cg+cg)
 //   chunks     [n_chunks][4] int32     {node_slot, tree_slot, row_start,
 //                                       row_count}
 //
@@ -66,8 +76,8 @@ static __device__ __forceinline__ unsigned wang_hash(unsigned s) {
 
 // ---------------------------------------------------------------------- //
 // K1: histogram build
-// grid: (n_chunks, n_feature_groups), block 256
-// dynamic LDS: fg * nbins * S floats
+// grid: (n_chunks, n_feature_groups[, n_class_groups]), block 256
+// dynamic LDS: fg * nbins * S floats (class-grouped: fg * nbins * cg)
 // ---------------------------------------------------------------------- //
 typedef __attribute__((ext_vector_type(4))) unsigned char uchar4v;
 
@@ -93,7 +103,12 @@ static __device__ __forceinline__ void hist_cell_add(
 // keeps the row count C = Σ m.  The __restrict__ qualifiers stay on the
 // kernel wrappers' own parameters: repeated here they only add per-call
 // alias scopes on top of the same facts.
-template <bool ROW_W>
+//
+// GROUPED (classification only): the block with blockIdx.z = z keeps the
+// classes [z*cg, z*cg + cg) and skips every row of another class, so its
+// tile is fg * nbins * cg floats whatever S is.  Each row is still counted
+// once across the class groups; only the row scan repeats per group.
+template <bool ROW_W, bool GROUPED>
 static __device__ __forceinline__ void tree_hist_body(
     const unsigned char* codes,    // [n][fp] row-major
     const int* y_int,              // [n] (cls) or nullptr
@@ -103,17 +118,21 @@ static __device__ __forceinline__ void tree_hist_body(
     const int* sample_idx,         // [TB][n]
     const int* chunks,             // [n_chunks][4]
     float* hist,                   // [NF][f][nbins][S]
-    long long n, int f, int fp, int nbins, int S, int is_cls, int fg) {
+    long long n, int f, int fp, int nbins, int S, int is_cls, int fg,
+    int cg) {
     extern __shared__ float lds[];
     const int chunk = blockIdx.x;
     const int g0 = blockIdx.y * fg;
     const int nf_g = min(fg, f - g0);
+    // first class and stat width of this block's tile
+    const int c0 = GROUPED ? (int)blockIdx.z * cg : 0;
+    const int cw = GROUPED ? min(cg, S - c0) : S;
     const int node_slot = chunks[chunk * 4 + 0];
     const int tree_slot = chunks[chunk * 4 + 1];
     const int row_start = chunks[chunk * 4 + 2];
     const int row_count = chunks[chunk * 4 + 3];
 
-    const int lds_sz = nf_g * nbins * S;
+    const int lds_sz = nf_g * nbins * cw;
     for (int i = threadIdx.x; i < lds_sz; i += blockDim.x) lds[i] = 0.f;
     __syncthreads();
 
@@ -130,6 +149,10 @@ static __device__ __forceinline__ void tree_hist_body(
         float v1 = 0.f, v2 = 0.f;
         if (is_cls) {
             stat = y_int[i];
+            if (GROUPED) {
+                stat -= c0;
+                if ((unsigned)stat >= (unsigned)cw) continue;
+            }
         } else {
             const float yv = y_f[i];
             v1 = w * yv;
@@ -145,14 +168,14 @@ static __device__ __forceinline__ void tree_hist_body(
                     const int jj = q * 4 + t;
                     if (jj >= nf_g) break;
                     hist_cell_add<ROW_W>(
-                        lds + ((jj * nbins + (int)b4[t]) * S), is_cls, stat,
+                        lds + ((jj * nbins + (int)b4[t]) * cw), is_cls, stat,
                         w, v1, v2, m);
                 }
             }
         } else {
             for (int jj = 0; jj < nf_g; ++jj)
                 hist_cell_add<ROW_W>(
-                    lds + ((jj * nbins + (int)crow[jj]) * S), is_cls, stat,
+                    lds + ((jj * nbins + (int)crow[jj]) * cw), is_cls, stat,
                     w, v1, v2, m);
         }
     }
@@ -161,7 +184,13 @@ static __device__ __forceinline__ void tree_hist_body(
     float* gh = hist + ((long long)node_slot * f + g0) * nbins * S;
     for (int i = threadIdx.x; i < lds_sz; i += blockDim.x) {
         const float v = lds[i];
-        if (v != 0.f) atomicAdd(gh + i, v);
+        if (v == 0.f) continue;
+        if (GROUPED) {
+            const int cell = i / cw;   // (feature, bin) of the tile
+            atomicAdd(gh + (long long)cell * S + c0 + (i - cell * cw), v);
+        } else {
+            atomicAdd(gh + i, v);
+        }
     }
 }
 
@@ -171,8 +200,21 @@ extern "C" __global__ __launch_bounds__(256) void k_tree_hist(
     const int* __restrict__ sample_idx, const int* __restrict__ chunks,
     float* __restrict__ hist, long long n, int f, int fp, int nbins, int S,
     int is_cls, int fg) {
-    tree_hist_body<false>(codes, y_int, y_f, nullptr, weights, sample_idx,
-                          chunks, hist, n, f, fp, nbins, S, is_cls, fg);
+    tree_hist_body<false, false>(codes, y_int, y_f, nullptr, weights,
+                                 sample_idx, chunks, hist, n, f, fp, nbins,
+                                 S, is_cls, fg, 0);
+}
+
+// grid.z = class groups of cg; dynamic LDS: fg * nbins * min(cg, S) floats
+extern "C" __global__ __launch_bounds__(256) void k_tree_hist_cg(
+    const unsigned char* __restrict__ codes, const int* __restrict__ y_int,
+    const unsigned char* __restrict__ weights,
+    const int* __restrict__ sample_idx, const int* __restrict__ chunks,
+    float* __restrict__ hist, long long n, int f, int fp, int nbins, int S,
+    int fg, int cg) {
+    tree_hist_body<false, true>(codes, y_int, nullptr, nullptr, weights,
+                                sample_idx, chunks, hist, n, f, fp, nbins,
+                                S, 1, fg, cg);
 }
 
 // dynamic LDS: fg * nbins * 4 floats
@@ -183,8 +225,9 @@ extern "C" __global__ __launch_bounds__(256) void k_tree_hist_w(
     const int* __restrict__ sample_idx, const int* __restrict__ chunks,
     float* __restrict__ hist, long long n, int f, int fp, int nbins,
     int fg) {
-    tree_hist_body<true>(codes, nullptr, y_f, row_w, weights, sample_idx,
-                         chunks, hist, n, f, fp, nbins, 4, 0, fg);
+    tree_hist_body<true, false>(codes, nullptr, y_f, row_w, weights,
+                                sample_idx, chunks, hist, n, f, fp, nbins,
+                                4, 0, fg, 0);
 }
 
 // ---------------------------------------------------------------------- //
@@ -255,6 +298,104 @@ static __device__ __forceinline__ bool split_candidate(
     return true;
 }
 
+// exact m-of-f feature subsample: a feature is kept when its hash ranks in
+// the m smallest.  Returns the m-th smallest hash value (binary search, the
+// whole block counts per step); every thread of the block calls it.
+static __device__ __forceinline__ unsigned feat_hash_threshold(
+    unsigned seed, int f, int m_features) {
+    __shared__ int s_cnt;
+    const int tid = threadIdx.x;
+    unsigned lo = 0u, hi = 0xffffffffu;
+    for (int it = 0; it < 32; ++it) {
+        const unsigned mid = lo + ((hi - lo) >> 1);
+        if (tid == 0) s_cnt = 0;
+        __syncthreads();
+        int cnt = 0;
+        for (int j = tid; j < f; j += blockDim.x)
+            if (wang_hash(seed ^ (unsigned)(j * 2654435761u)) <= mid)
+                ++cnt;
+        atomicAdd(&s_cnt, cnt);
+        __syncthreads();
+        const int total = s_cnt;
+        __syncthreads();
+        if (total >= m_features) hi = mid; else lo = mid + 1;
+        if (lo >= hi) break;
+    }
+    return hi;
+}
+
+// The ending both scans share.  Lane 0 of every wave brings its wave's best
+// candidate; thread 0 merges them (larger gain, then lower feature, lower
+// bin) and writes the node's decision, then the block writes the parent
+// totals and the winning split's left stats.
+template <bool MISSING>
+static __device__ __forceinline__ void split_block_finish(
+    float best_gain, int best_feat, int best_bin, float best_wl, int best_ml,
+    const float* s_parent, float imp_p, const float* H, int node, int nbins,
+    int S, int* __restrict__ out_feat, int* __restrict__ out_bin,
+    float* __restrict__ out_wl, float* __restrict__ out_gain,
+    float* __restrict__ out_imp, float* __restrict__ out_stats,
+    float* __restrict__ out_lstats, int* __restrict__ out_mleft) {
+    __shared__ float s_best_gain[256 / WAVE];
+    __shared__ int s_best_feat[256 / WAVE];
+    __shared__ int s_best_bin[256 / WAVE];
+    __shared__ float s_best_wl[256 / WAVE];
+    __shared__ int s_best_ml[MISSING ? 256 / WAVE : 1];
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wid = tid / WAVE;
+    if (lane == 0) {
+        s_best_gain[wid] = best_gain;
+        s_best_feat[wid] = best_feat;
+        s_best_bin[wid] = best_bin;
+        s_best_wl[wid] = best_wl;
+        if (MISSING) s_best_ml[wid] = best_ml;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        for (int w2 = 1; w2 < (int)(blockDim.x / WAVE); ++w2) {
+            const float og = s_best_gain[w2];
+            const int of = s_best_feat[w2];
+            const bool take = (og > s_best_gain[0] + 1e-12f) ||
+                              (og > s_best_gain[0] - 1e-12f && of >= 0 &&
+                               (s_best_feat[0] < 0 ||
+                                of < s_best_feat[0] ||
+                                (of == s_best_feat[0] &&
+                                 s_best_bin[w2] < s_best_bin[0])));
+            if (take) {
+                s_best_gain[0] = og;
+                s_best_feat[0] = of;
+                s_best_bin[0] = s_best_bin[w2];
+                s_best_wl[0] = s_best_wl[w2];
+                if (MISSING) s_best_ml[0] = s_best_ml[w2];
+            }
+        }
+        out_feat[node] = s_best_gain[0] > 0.f ? s_best_feat[0] : -1;
+        out_bin[node] = s_best_bin[0];
+        out_wl[node] = s_best_wl[0];
+        out_gain[node] = s_best_gain[0];
+        out_imp[node] = imp_p;
+        if (MISSING)
+            out_mleft[node] = s_best_gain[0] > 0.f ? s_best_ml[0] : 0;
+    }
+    for (int c = tid; c < S; c += blockDim.x)
+        out_stats[(long long)node * S + c] = s_parent[c];
+    __syncthreads();
+    // left stats of the winning split (prefix sum over its bins, then the
+    // missing bin when it goes left: all zeros there on a majority flag)
+    const int wf = (s_best_gain[0] > 0.f) ? s_best_feat[0] : -1;
+    for (int c = tid; c < S; c += blockDim.x) {
+        float acc = 0.f;
+        if (wf >= 0) {
+            const float* Hw = H + (long long)wf * nbins * S;
+            const int wb = s_best_bin[0];
+            for (int b = 0; b <= wb; ++b) acc += Hw[b * S + c];
+            if (MISSING && s_best_ml[0]) acc += Hw[(nbins - 1) * S + c];
+        }
+        out_lstats[(long long)node * S + c] = acc;
+    }
+}
+
 template <bool COUNTED, bool MISSING>
 static __device__ __forceinline__ void tree_split_body(
     const float* __restrict__ hist,        // [NF][f][nbins][S]
@@ -276,12 +417,6 @@ static __device__ __forceinline__ void tree_split_body(
     const int tid = threadIdx.x;
 
     __shared__ float s_parent[36];     // S <= 32 stats + pad
-    __shared__ int s_cnt;
-    __shared__ float s_best_gain[256 / WAVE];
-    __shared__ int s_best_feat[256 / WAVE];
-    __shared__ int s_best_bin[256 / WAVE];
-    __shared__ float s_best_wl[256 / WAVE];
-    __shared__ int s_best_ml[MISSING ? 256 / WAVE : 1];
 
     // parent totals from feature 0's histogram
     for (int c = tid; c < S; c += blockDim.x) s_parent[c] = 0.f;
@@ -297,28 +432,8 @@ static __device__ __forceinline__ void tree_split_body(
     }
     const float imp_p = impurity(s_parent, wp, S, is_cls, crit);
 
-    // exact m-of-f feature subsample: keep features whose hash ranks in
-    // the m smallest (binary search for the m-th smallest hash value)
     unsigned h_thresh = 0xffffffffu;
-    if (m_features < f) {
-        unsigned lo = 0u, hi = 0xffffffffu;
-        for (int it = 0; it < 32; ++it) {
-            const unsigned mid = lo + ((hi - lo) >> 1);
-            if (tid == 0) s_cnt = 0;
-            __syncthreads();
-            int cnt = 0;
-            for (int j = tid; j < f; j += blockDim.x)
-                if (wang_hash(seed ^ (unsigned)(j * 2654435761u)) <= mid)
-                    ++cnt;
-            atomicAdd(&s_cnt, cnt);
-            __syncthreads();
-            const int total = s_cnt;
-            __syncthreads();
-            if (total >= m_features) hi = mid; else lo = mid + 1;
-            if (lo >= hi) break;
-        }
-        h_thresh = hi;
-    }
+    if (m_features < f) h_thresh = feat_hash_threshold(seed, f, m_features);
 
     // per-thread best over its features
     float best_gain = -1.f;
@@ -413,8 +528,6 @@ static __device__ __forceinline__ void tree_split_body(
     }
 
     // wave then block argmax reduce (lower (feat,bin) wins ties)
-    const int lane = tid & (WAVE - 1);
-    const int wid = tid / WAVE;
     for (int off = WAVE / 2; off > 0; off >>= 1) {
         const float og = __shfl_down(best_gain, off);
         const int of = __shfl_down(best_feat, off);
@@ -430,56 +543,234 @@ static __device__ __forceinline__ void tree_split_body(
             best_ml = oml;
         }
     }
-    if (lane == 0) {
-        s_best_gain[wid] = best_gain;
-        s_best_feat[wid] = best_feat;
-        s_best_bin[wid] = best_bin;
-        s_best_wl[wid] = best_wl;
-        if (MISSING) s_best_ml[wid] = best_ml;
+    split_block_finish<MISSING>(best_gain, best_feat, best_bin, best_wl,
+                                best_ml, s_parent, imp_p, H, node, nbins, S,
+                                out_feat, out_bin, out_wl, out_gain, out_imp,
+                                out_stats, out_lstats, out_mleft);
+}
+
+// ---------------------------------------------------------------------- //
+// K2 wide: classification with 32 < S <= 256 — 256 threads per frontier
+// node, ONE WAVE PER FEATURE.  Wave w scans the w-th contiguous quarter of
+// the features, in order: the block ending keeps the earlier wave's
+// candidate when two gains are exactly equal, which is then the lower
+// feature, as in the narrow scan (features identical within the node are
+// common once a node holds two or three separable classes).  Lane l owns
+// the classes l, l+64, l+128, l+192: at most WIDE_K running left counts (and
+// missing-bin counts) per lane, and per bin one coalesced load of
+// H[j][b][.] along S.  Everything summed over the classes is a wave
+// reduction (xor butterfly: a fixed order, the same value in every lane), so
+// the scan's control flow is wave-uniform.  Candidates, validity, gain,
+// subsample, ExtraTrees bin and tie order are tree_split_body's.
+// ---------------------------------------------------------------------- //
+#define WIDE_S 256
+#define WIDE_K (WIDE_S / WAVE)
+
+static __device__ __forceinline__ float wave_sum(float v) {
+    for (int off = WAVE / 2; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    return v;
+}
+
+// impurity() over a stats vector spread across the wave (s = this lane's
+// WIDE_K classes, zero past S); w is the vector's total
+static __device__ __forceinline__ float
+impurity_wide(const float* s, float w, int crit) {
+    if (w <= 0.f) return 0.f;
+    float a = 0.f;
+    if (crit == CRIT_GINI) {
+#pragma unroll
+        for (int k = 0; k < WIDE_K; ++k) a += s[k] * s[k];
+        return 1.f - wave_sum(a) / (w * w);
+    }
+#pragma unroll
+    for (int k = 0; k < WIDE_K; ++k) {
+        if (s[k] > 0.f) {
+            const float p = s[k] / w;
+            a -= p * __log2f(p);
+        }
+    }
+    return wave_sum(a);
+}
+
+// split_candidate<false> on lane-sliced stats
+static __device__ __forceinline__ bool split_candidate_wide(
+    const float* left, float wl, const float* parent, float wp, float imp_p,
+    int crit, float min_leaf_w, float* gain_out) {
+    const float wr = wp - wl;
+    if (wl < min_leaf_w || wr < min_leaf_w) return false;
+    const float imp_l = impurity_wide(left, wl, crit);
+    float right[WIDE_K];
+#pragma unroll
+    for (int k = 0; k < WIDE_K; ++k) right[k] = parent[k] - left[k];
+    const float imp_r = impurity_wide(right, wr, crit);
+    *gain_out = imp_p - (wl * imp_l + wr * imp_r) / wp;
+    return true;
+}
+
+template <bool MISSING>
+static __device__ __forceinline__ void tree_split_wide_body(
+    const float* __restrict__ hist,        // [NF][f][nbins][S]
+    const unsigned* __restrict__ node_seed,  // [NF]
+    int f, int nbins, int S, int crit, int m_features, int extra_mode,
+    float min_leaf_w, int* __restrict__ out_feat, int* __restrict__ out_bin,
+    float* __restrict__ out_wl, float* __restrict__ out_gain,
+    float* __restrict__ out_imp, float* __restrict__ out_stats,
+    float* __restrict__ out_lstats, int* __restrict__ out_mleft) {
+    const int node = blockIdx.x;
+    const unsigned seed = node_seed[node];
+    const float* H = hist + (long long)node * f * nbins * S;
+    const int tid = threadIdx.x;
+    const int lane = tid & (WAVE - 1);
+    const int wid = tid / WAVE;
+
+    __shared__ float s_parent[WIDE_S];
+
+    // parent totals from feature 0's histogram: thread c sums class c
+    for (int c = tid; c < WIDE_S; c += blockDim.x) {
+        float acc = 0.f;
+        if (c < S)
+            for (int b = 0; b < nbins; ++b) acc += H[b * S + c];
+        s_parent[c] = acc;
     }
     __syncthreads();
-    if (tid == 0) {
-        for (int w2 = 1; w2 < (int)(blockDim.x / WAVE); ++w2) {
-            const float og = s_best_gain[w2];
-            const int of = s_best_feat[w2];
-            const bool take = (og > s_best_gain[0] + 1e-12f) ||
-                              (og > s_best_gain[0] - 1e-12f && of >= 0 &&
-                               (s_best_feat[0] < 0 ||
-                                of < s_best_feat[0] ||
-                                (of == s_best_feat[0] &&
-                                 s_best_bin[w2] < s_best_bin[0])));
-            if (take) {
-                s_best_gain[0] = og;
-                s_best_feat[0] = of;
-                s_best_bin[0] = s_best_bin[w2];
-                s_best_wl[0] = s_best_wl[w2];
-                if (MISSING) s_best_ml[0] = s_best_ml[w2];
+    float parent[WIDE_K];
+    float wsum = 0.f;
+#pragma unroll
+    for (int k = 0; k < WIDE_K; ++k) {
+        parent[k] = s_parent[lane + k * WAVE];
+        wsum += parent[k];
+    }
+    const float wp = wave_sum(wsum);
+    const float imp_p = impurity_wide(parent, wp, crit);
+
+    unsigned h_thresh = 0xffffffffu;
+    if (m_features < f) h_thresh = feat_hash_threshold(seed, f, m_features);
+
+    // per-wave best over its features (the same value in every lane)
+    float best_gain = -1.f;
+    int best_feat = -1, best_bin = -1;
+    float best_wl = 0.f;
+    int best_ml = 0;
+    float left[WIDE_K];
+    float miss[MISSING ? WIDE_K : 1];   // the feature's missing-bin stats
+    float lm[MISSING ? WIDE_K : 1];     // left + miss: the L candidate
+    const int n_waves = blockDim.x / WAVE;
+    const int per_wave = (f + n_waves - 1) / n_waves;
+    const int j_end = min(f, (wid + 1) * per_wave);
+    for (int j = wid * per_wave; j < j_end; ++j) {
+        if (m_features < f &&
+            wang_hash(seed ^ (unsigned)(j * 2654435761u)) > h_thresh)
+            continue;
+        const float* Hj = H + (long long)j * nbins * S;
+        // ExtraTrees: pick one random bin in the node's occupied range (a
+        // bin of non-negative counts holds weight iff some class does)
+        int rand_bin = -1;
+        if (extra_mode) {
+            int lo = -1, hi = -1;
+            for (int b = 0; b < nbins; ++b) {
+                bool occ = false;
+#pragma unroll
+                for (int k = 0; k < WIDE_K; ++k) {
+                    const int c = lane + k * WAVE;
+                    if (c < S && Hj[b * S + c] > 0.f) occ = true;
+                }
+                if (__any(occ)) {
+                    if (lo < 0) lo = b;
+                    hi = b;
+                }
+            }
+            if (lo < 0 || hi <= lo) continue;  // constant feature here
+            const unsigned r = wang_hash(seed ^ 0x9e3779b9u ^
+                                         (unsigned)(j * 40503u));
+            rand_bin = lo + (int)(r % (unsigned)(hi - lo));  // in [lo, hi)
+        }
+#pragma unroll
+        for (int k = 0; k < WIDE_K; ++k) left[k] = 0.f;
+        float wm = 0.f;
+        if (MISSING) {
+            float s = 0.f;
+#pragma unroll
+            for (int k = 0; k < WIDE_K; ++k) {
+                const int c = lane + k * WAVE;
+                miss[k] = c < S ? Hj[(nbins - 1) * S + c] : 0.f;
+                s += miss[k];
+            }
+            wm = wave_sum(s);
+        }
+        // the ExtraTrees cut needs the prefix up to its one bin only
+        const int b_end = extra_mode ? rand_bin + 1 : nbins - 1;
+        for (int b = 0; b < b_end; ++b) {
+            float s = 0.f;
+#pragma unroll
+            for (int k = 0; k < WIDE_K; ++k) {
+                const int c = lane + k * WAVE;
+                if (c < S) left[k] += Hj[b * S + c];
+                s += left[k];
+            }
+            if (extra_mode && b != rand_bin) continue;
+            const float wl = wave_sum(s);
+            float gain;
+            if (split_candidate_wide(left, wl, parent, wp, imp_p, crit,
+                                     min_leaf_w, &gain)) {
+                if (gain > best_gain + 1e-12f) {
+                    best_gain = gain;
+                    best_feat = j;
+                    best_bin = b;
+                    best_wl = wl;
+                    // no missing weight here: majority side
+                    if (MISSING) best_ml = (!(wm > 0.f) && wl + wl > wp);
+                }
+            }
+            if (MISSING && wm > 0.f) {
+                float sm = 0.f;
+#pragma unroll
+                for (int k = 0; k < WIDE_K; ++k) {
+                    lm[k] = left[k] + miss[k];
+                    sm += lm[k];
+                }
+                const float wlm = wave_sum(sm);
+                if (split_candidate_wide(lm, wlm, parent, wp, imp_p, crit,
+                                         min_leaf_w, &gain) &&
+                    gain > best_gain + 1e-12f) {
+                    best_gain = gain;
+                    best_feat = j;
+                    best_bin = b;
+                    best_wl = wlm;
+                    best_ml = 1;
+                }
             }
         }
-        out_feat[node] = s_best_gain[0] > 0.f ? s_best_feat[0] : -1;
-        out_bin[node] = s_best_bin[0];
-        out_wl[node] = s_best_wl[0];
-        out_gain[node] = s_best_gain[0];
-        out_imp[node] = imp_p;
-        if (MISSING)
-            out_mleft[node] = s_best_gain[0] > 0.f ? s_best_ml[0] : 0;
     }
-    for (int c = tid; c < S; c += blockDim.x)
-        out_stats[(long long)node * S + c] = s_parent[c];
-    __syncthreads();
-    // left stats of the winning split (prefix sum over its bins, then the
-    // missing bin when it goes left: all zeros there on a majority flag)
-    const int wf = (s_best_gain[0] > 0.f) ? s_best_feat[0] : -1;
-    for (int c = tid; c < S; c += blockDim.x) {
-        float acc = 0.f;
-        if (wf >= 0) {
-            const float* Hw = H + (long long)wf * nbins * S;
-            const int wb = s_best_bin[0];
-            for (int b = 0; b <= wb; ++b) acc += Hw[b * S + c];
-            if (MISSING && s_best_ml[0]) acc += Hw[(nbins - 1) * S + c];
-        }
-        out_lstats[(long long)node * S + c] = acc;
-    }
+    split_block_finish<MISSING>(best_gain, best_feat, best_bin, best_wl,
+                                best_ml, s_parent, imp_p, H, node, nbins, S,
+                                out_feat, out_bin, out_wl, out_gain, out_imp,
+                                out_stats, out_lstats, out_mleft);
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_tree_split_wide(
+    const float* __restrict__ hist, const unsigned* __restrict__ node_seed,
+    int f, int nbins, int S, int crit, int m_features, int extra_mode,
+    float min_leaf_w, int* __restrict__ out_feat, int* __restrict__ out_bin,
+    float* __restrict__ out_wl, float* __restrict__ out_gain,
+    float* __restrict__ out_imp, float* __restrict__ out_stats,
+    float* __restrict__ out_lstats) {
+    tree_split_wide_body<false>(hist, node_seed, f, nbins, S, crit,
+                                m_features, extra_mode, min_leaf_w, out_feat,
+                                out_bin, out_wl, out_gain, out_imp,
+                                out_stats, out_lstats, nullptr);
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_tree_split_wide_m(
+    const float* __restrict__ hist, const unsigned* __restrict__ node_seed,
+    int f, int nbins, int S, int crit, int m_features, float min_leaf_w,
+    int* __restrict__ out_feat, int* __restrict__ out_bin,
+    float* __restrict__ out_wl, float* __restrict__ out_gain,
+    float* __restrict__ out_imp, float* __restrict__ out_stats,
+    float* __restrict__ out_lstats, int* __restrict__ out_mleft) {
+    tree_split_wide_body<true>(hist, node_seed, f, nbins, S, crit,
+                               m_features, 0, min_leaf_w, out_feat, out_bin,
+                               out_wl, out_gain, out_imp, out_stats,
+                               out_lstats, out_mleft);
 }
 
 extern "C" __global__ __launch_bounds__(256) void k_tree_split(
@@ -662,18 +953,31 @@ extern "C" hipError_t skdist_tree_hist(
     const void* codes, const void* y_int, const void* y_f,
     const void* row_w, const void* weights, const void* sample_idx,
     const void* chunks, void* hist, long long n, int f, int fp, int nbins,
-    int S, int fg, int n_chunks, hipStream_t stream) {
+    int S, int fg, int cg, int n_chunks, hipStream_t stream) {
     if (n_chunks <= 0) return hipSuccess;
-    const size_t lds = (size_t)fg * nbins * S * sizeof(float);
+    if (cg < 0 || S <= 0) return hipErrorInvalidValue;
+    // the tile's stat width: all S stats, or one class group
+    const int tile_s = cg > 0 && cg < S ? cg : S;
+    const size_t lds = (size_t)fg * nbins * tile_s * sizeof(float);
     if (fg <= 0 || f <= 0 || fp % 4 != 0 || f > fp || nbins <= 0 ||
-        nbins > 256 || S <= 0 || lds > 64 * 1024)
+        nbins > 256 || lds > 64 * 1024)
         return hipErrorInvalidValue;
     // exactly one target; row_w rides the regression stats only (S = 4)
     if ((y_int != nullptr) == (y_f != nullptr) ||
         (row_w != nullptr && (y_f == nullptr || S != 4)))
         return hipErrorInvalidValue;
-    const dim3 grid(n_chunks, (f + fg - 1) / fg);
-    if (row_w != nullptr)
+    // class groups split class counts only
+    const int n_cg = cg > 0 ? (S + cg - 1) / cg : 1;
+    if (cg > 0 && (y_int == nullptr || row_w != nullptr || n_cg > 65535))
+        return hipErrorInvalidValue;
+    const dim3 grid(n_chunks, (f + fg - 1) / fg, n_cg);
+    if (cg > 0)
+        hipLaunchKernelGGL(k_tree_hist_cg, grid, dim3(256), lds, stream,
+                           (const unsigned char*)codes, (const int*)y_int,
+                           (const unsigned char*)weights,
+                           (const int*)sample_idx, (const int*)chunks,
+                           (float*)hist, n, f, fp, nbins, S, fg, cg);
+    else if (row_w != nullptr)
         hipLaunchKernelGGL(k_tree_hist_w, grid, dim3(256), lds, stream,
                            (const unsigned char*)codes, (const float*)y_f,
                            (const float*)row_w,
@@ -698,11 +1002,37 @@ extern "C" hipError_t skdist_tree_split(
     void* out_wl, void* out_gain, void* out_imp, void* out_stats,
     void* out_lstats, int missing, void* out_mleft, hipStream_t stream) {
     if (n_frontier <= 0) return hipSuccess;
-    if (S <= 0 || S > 32 || cnt_stat >= S) return hipErrorInvalidValue;
+    if (S <= 0 || S > WIDE_S || cnt_stat >= S) return hipErrorInvalidValue;
+    // above 32 stats only the class-count scan exists (the counted variant
+    // is a regression one)
+    const bool wide = S > 32;
+    if (wide && (!is_cls || cnt_stat >= 0)) return hipErrorInvalidValue;
     // the missing scan needs a present bin below the missing one, its own
     // output, and has no ExtraTrees mode
     if (missing && (nbins < 2 || out_mleft == nullptr || extra_mode))
         return hipErrorInvalidValue;
+    if (wide) {
+        // one wave per feature, four waves with a quarter of them each
+        const dim3 grid(n_frontier), block(256);
+        if (missing)
+            hipLaunchKernelGGL(k_tree_split_wide_m, grid, block, 0, stream,
+                               (const float*)hist,
+                               (const unsigned*)node_seed, f, nbins, S, crit,
+                               m_features, min_leaf, (int*)out_feat,
+                               (int*)out_bin, (float*)out_wl,
+                               (float*)out_gain, (float*)out_imp,
+                               (float*)out_stats, (float*)out_lstats,
+                               (int*)out_mleft);
+        else
+            hipLaunchKernelGGL(k_tree_split_wide, grid, block, 0, stream,
+                               (const float*)hist,
+                               (const unsigned*)node_seed, f, nbins, S, crit,
+                               m_features, extra_mode, min_leaf,
+                               (int*)out_feat, (int*)out_bin, (float*)out_wl,
+                               (float*)out_gain, (float*)out_imp,
+                               (float*)out_stats, (float*)out_lstats);
+        return hipGetLastError();
+    }
     // per-node parallelism is one thread per feature: size the block to
     // f so low-f datasets don't idle 3/4 of each workgroup
     const int threads = f >= 192 ? 256 : (f >= 96 ? 128 : 64);

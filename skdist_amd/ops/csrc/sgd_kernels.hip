@@ -17,7 +17,8 @@
 //
 // Layouts (row-major, K-contiguous):
 //   Xs    [n_pad][fa]        bf16  epoch-shuffled, rows n..n_pad zero
-//   XsT   [fa_store][n_pad]  bf16  transpose (fa_store = ceil(fa/128)*128)
+//   XsT   [fa_store][n_pad]  bf16  transpose (fa_store = ceil(fa/128)*128;
+//                                rows fa..fa_store zero)
 //   WbfT  [ncols_pad][fa]    bf16
 //   W, V  [fa][ncols_pad]    f32
 //   GT    [ncols_pad][gts]   bf16
@@ -57,8 +58,70 @@ frag_load(const __bf16* lds, int row, int fk) {
 // ---------------------------------------------------------------------- //
 // K1: fused forward GEMM + loss gradient + transposed store
 // grid: (m_pad/BM, ncols_pad/BN), block 256
+//
+// The epilogue (64 accumulators per lane -> masked dloss -> bf16) costs
+// more issue slots than the GEMM loop, so it is instantiated per loss and
+// per path and the kernel branches once, workgroup-uniformly:
+//   PLAIN   every column of the tile has col_class < 0 and col_class2 < 0
+//           (pad columns included) and there is no row_w: t = y, g is not
+//           scaled, and an element trains when its row may train and the
+//           row's fold differs from the column's.
+//   general class targets, one-vs-one pairs, row_w.
+// Both paths run the same arithmetic on an element both can express
+// (dropping a multiply by 1.0f is exact), so GT does not depend on which
+// path a tile took.  ok_s holds, per row, whether bm + row < m.
+//
+// __launch_bounds__(256, 4): 4 waves per SIMD, i.e. 4 workgroups per CU.
+// Within 128 registers the accumulators stay in VGPRs (121 VGPRs, no
+// AGPRs, no scratch); unbounded, the kernel took 121 + 64 and ran 2.
 // ---------------------------------------------------------------------- //
-extern "C" __global__ __launch_bounds__(256) void k_fwd_gt(
+template <int LOSS, bool PLAIN>
+static __device__ __forceinline__ void fwd_epilogue(
+    const f32x4 (&acc)[4][4], __bf16* ldsC, const float* y_s,
+    const int* fold_s, const int* ok_s, const float* rw_s,
+    const int* cls_s, const int* cfold_s, const int* cls2_s,
+    int wr, int wc, int fr, int rw)
+{
+    #pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+        const int rowb = wr + mi * 16 + rw * 4;
+        const f32x4 y4 = *(const f32x4*)&y_s[rowb];
+        const int4v fo4 = *(const int4v*)&fold_s[rowb];
+        const int4v ok4 = *(const int4v*)&ok_s[rowb];
+        f32x4 rw4 = {1.f, 1.f, 1.f, 1.f};
+        if (!PLAIN) rw4 = *(const f32x4*)&rw_s[rowb];
+        #pragma unroll
+        for (int ni = 0; ni < 4; ++ni) {
+            const int colb = wc + ni * 16 + fr;
+            const int cfo = cfold_s[colb];
+            const int cls = PLAIN ? -1 : cls_s[colb];
+            const int c2 = PLAIN ? -1 : cls2_s[colb];
+            short4v g4;
+            #pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float z = acc[mi][ni][r];
+                const float yv = y4[r];
+                bool train = (fo4[r] != cfo) && (ok4[r] != 0);
+                float g;
+                if (PLAIN) {
+                    g = dloss(LOSS, z, yv);
+                } else {
+                    const float t =
+                        (cls < 0) ? yv : (yv == (float)cls ? 1.f : 0.f);
+                    g = dloss(LOSS, z, t) * rw4[r];
+                    if (c2 >= 0)  // one-vs-one: only the pair's rows train
+                        train = train &&
+                                (yv == (float)cls || yv == (float)c2);
+                }
+                g4[r] = __builtin_bit_cast(short,
+                                           f32_to_bf16(train ? g : 0.f));
+            }
+            *(short4v*)&ldsC[colb * LDC + rowb] = g4;
+        }
+    }
+}
+
+extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt(
     const __bf16* __restrict__ Xs,    // [n_pad][fa]
     const __bf16* __restrict__ WbfT,  // [ncols_pad][fa]
     __bf16* __restrict__ GT,          // [ncols_pad][gt_stride]
@@ -82,6 +145,8 @@ extern "C" __global__ __launch_bounds__(256) void k_fwd_gt(
     int* cfold_s = (int*)(meta + 1536);     // [BN]
     int* cls2_s = (int*)(meta + 2048);      // [BN]
     float* rw_s = (float*)(meta + 2560);    // [BM]
+    int* ok_s = (int*)(meta + 3072);        // [BM] row may train (< m)
+    int* gen_s = (int*)(meta + 3584);       // [2] a wave saw a class column
 
     const int tid = threadIdx.x;
     const int bm = blockIdx.x * BM;
@@ -95,11 +160,16 @@ extern "C" __global__ __launch_bounds__(256) void k_fwd_gt(
         y_s[tid] = ok ? y[r] : 0.f;
         fold_s[tid] = ok ? fold[r] : -9;
         rw_s[tid] = (row_w != nullptr && ok) ? row_w[r] : 1.f;
+        ok_s[tid] = (bm + tid < m) ? 1 : 0;
     } else {
         const int c = tid - BM;
-        cls_s[c] = col_class[bn + c];
+        const int cl = col_class[bn + c];
+        const int c2 = col_class2[bn + c];
+        cls_s[c] = cl;
         cfold_s[c] = col_fold[bn + c];
-        cls2_s[c] = col_class2[bn + c];
+        cls2_s[c] = c2;
+        const bool general = __ballot(cl >= 0 || c2 >= 0) != 0ull;
+        if (lane == 0) gen_s[w - 2] = general ? 1 : 0;
     }
 
     const __bf16* Abase = Xs + (long long)(start + bm) * fa;
@@ -139,37 +209,30 @@ extern "C" __global__ __launch_bounds__(256) void k_fwd_gt(
         cur ^= 1;
     }
 
-    // epilogue: z -> masked dloss -> bf16, transposed through LDS
+    // epilogue: z -> masked dloss -> bf16, transposed through LDS.  The
+    // barrier also orders the prologue's metadata writes (nk >= 1 put
+    // another one in between) before the reads below.
     __syncthreads();
     const int rw = lane >> 4;
-    #pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
-        #pragma unroll
-        for (int ni = 0; ni < 4; ++ni) {
-            const int rowb = wr + mi * 16 + rw * 4;
-            const int colb = wc + ni * 16 + fr;
-            const int cls = cls_s[colb];
-            const int cfo = cfold_s[colb];
-            const int c2 = cls2_s[colb];
-            short4v g4;
-            #pragma unroll
-            for (int r = 0; r < 4; ++r) {
-                const int row = rowb + r;
-                const float z = acc[mi][ni][r];
-                const float yv = y_s[row];
-                const float t =
-                    (cls < 0) ? yv : (yv == (float)cls ? 1.f : 0.f);
-                const float g = dloss(loss_id, z, t) * rw_s[row];
-                bool train = (fold_s[row] != cfo) && (bm + row < m);
-                if (c2 >= 0)  // one-vs-one: only the pair's rows train
-                    train = train &&
-                            (yv == (float)cls || yv == (float)c2);
-                g4[r] = __builtin_bit_cast(short,
-                                           f32_to_bf16(train ? g : 0.f));
-            }
-            *(short4v*)&ldsC[colb * LDC + rowb] = g4;
-        }
+    const bool plain = __builtin_amdgcn_readfirstlane(
+        (gen_s[0] | gen_s[1]) == 0 && row_w == nullptr);
+    #define FWD_EPILOGUE(L)                                                 \
+        do {                                                                \
+            if (plain)                                                      \
+                fwd_epilogue<L, true>(acc, ldsC, y_s, fold_s, ok_s, rw_s,   \
+                                      cls_s, cfold_s, cls2_s, wr, wc, fr,   \
+                                      rw);                                  \
+            else                                                            \
+                fwd_epilogue<L, false>(acc, ldsC, y_s, fold_s, ok_s, rw_s,  \
+                                       cls_s, cfold_s, cls2_s, wr, wc, fr,  \
+                                       rw);                                 \
+        } while (0)
+    switch (loss_id) {
+    case LOSS_LOG: FWD_EPILOGUE(LOSS_LOG); break;
+    case LOSS_HINGE: FWD_EPILOGUE(LOSS_HINGE); break;
+    default: FWD_EPILOGUE(LOSS_SQUARED); break;
     }
+    #undef FWD_EPILOGUE
     __syncthreads();
     #pragma unroll
     for (int i = 0; i < 4; ++i) {
@@ -186,9 +249,18 @@ extern "C" __global__ __launch_bounds__(256) void k_fwd_gt(
 
 // ---------------------------------------------------------------------- //
 // K2: Grad partial slabs, split-K over minibatch rows
-// grid: (fa_store/BM, ncols_pad/BN, SPLITK), block 256
+// grid: (ceil(fa/rows)*rows / rows, ncols_pad/BN, SPLITK), block 256
+//
+// The tile is rows x 128 with rows = 32 * MI: 2x2 waves, each holding MI
+// fragments of 16 feature rows by 4 of 16 columns.  MI = 4 is the 128-row
+// tile; MI = 3 is a 96-row tile for fa that 96 covers with fewer padded
+// rows (fa = 288: 3 x 96 against 3 x 128).  The A stage is then 6 chunks
+// of 16 rows (6 KiB) with the same XOR slot swizzle.  BK, the slab bounds
+// and the k order are those of the 128-row tile, so a partial element is
+// the same chain of MFMA accumulations under either.
 // ---------------------------------------------------------------------- //
-extern "C" __global__ __launch_bounds__(256) void k_grad_partial(
+template <int MI>
+static __device__ __forceinline__ void grad_partial_body(
     const __bf16* __restrict__ XsT,  // [fa_store][n_pad]
     const __bf16* __restrict__ GT,   // [ncols_pad][gt_stride]
     float* __restrict__ partial,     // [SPLITK][fa][ncols_pad]
@@ -197,9 +269,26 @@ extern "C" __global__ __launch_bounds__(256) void k_grad_partial(
 {
     extern __shared__ __attribute__((aligned(16))) char sm[];
 
+    // stage the (32 * MI) x 32 A tile: 2 * MI chunks of 16 rows, chunk c
+    // by wave c & 3 (wave-uniform guard)
+    #define STAGE_A(ldsbase, SRC_EXPR)                                      \
+        do {                                                                \
+            _Pragma("unroll") for (int i = 0; i < 2; ++i) {                 \
+                const int c = w + 4 * i;                                    \
+                if (c < 2 * MI) {                                           \
+                    const int row = 16 * c + (lane >> 2);                   \
+                    const int slot = (lane & 3) ^ ((row >> 2) & 3);         \
+                    const __bf16* _src = (SRC_EXPR) + slot * 8;             \
+                    __builtin_amdgcn_global_load_lds(                       \
+                        (const unsigned int*)_src,                          \
+                        (unsigned int*)((ldsbase) + c * 512), 16, 0, 0);    \
+                }                                                           \
+            }                                                               \
+        } while (0)
+
     const int tid = threadIdx.x;
-    const int bf = blockIdx.x * BM;   // feature-row offset
-    const int bn = blockIdx.y * BN;   // col offset
+    const int bf = blockIdx.x * (32 * MI);  // feature-row offset
+    const int bn = blockIdx.y * BN;         // col offset
     const int z = blockIdx.z;
     const int lane = tid & 63;
     const int w = tid >> 6;
@@ -210,45 +299,46 @@ extern "C" __global__ __launch_bounds__(256) void k_grad_partial(
     const int k0 = z * k_chunk;
     const int k1 = min(m_pad, k0 + k_chunk);
 
-    const int wr = ((w >> 1) & 1) * 64;
+    const int wr = ((w >> 1) & 1) * (16 * MI);
     const int wc = (w & 1) * 64;
     const int fr = lane & 15;
     const int fk = (lane >> 4) * 8;
 
-    f32x4 acc[4][4] = {};
+    f32x4 acc[MI][4] = {};
     int cur = 0;
     if (k0 < k1) {
-        STAGE_TILE(bufA(0), Abase + (long long)row * n_pad + k0);
+        STAGE_A(bufA(0), Abase + (long long)row * n_pad + k0);
         STAGE_TILE(bufB(0), Bbase + (long long)row * gt_stride + k0);
     }
     for (int kt = k0; kt < k1; kt += BK) {
         __syncthreads();
         if (kt + BK < k1) {
-            STAGE_TILE(bufA(cur ^ 1),
-                       Abase + (long long)row * n_pad + kt + BK);
+            STAGE_A(bufA(cur ^ 1),
+                    Abase + (long long)row * n_pad + kt + BK);
             STAGE_TILE(bufB(cur ^ 1),
                        Bbase + (long long)row * gt_stride + kt + BK);
         }
-        bf16x8 af[4], bfr[4];
+        bf16x8 af[MI], bfr[4];
         #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
+        for (int mi = 0; mi < MI; ++mi)
             af[mi] = frag_load(bufA(cur), wr + mi * 16 + fr, fk);
         #pragma unroll
         for (int ni = 0; ni < 4; ++ni)
             bfr[ni] = frag_load(bufB(cur), wc + ni * 16 + fr, fk);
         #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
+        for (int mi = 0; mi < MI; ++mi)
             #pragma unroll
             for (int ni = 0; ni < 4; ++ni)
                 acc[mi][ni] =
                     MFMA_BF16_16x16x32(af[mi], bfr[ni], acc[mi][ni]);
         cur ^= 1;
     }
+    #undef STAGE_A
 
     float* out = partial + (long long)z * fa * ncols_pad;
     const int rw = lane >> 4;
     #pragma unroll
-    for (int mi = 0; mi < 4; ++mi) {
+    for (int mi = 0; mi < MI; ++mi) {
         const int rowb = bf + wr + mi * 16 + rw * 4;
         #pragma unroll
         for (int ni = 0; ni < 4; ++ni) {
@@ -261,6 +351,26 @@ extern "C" __global__ __launch_bounds__(256) void k_grad_partial(
             }
         }
     }
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_grad_partial(
+    const __bf16* __restrict__ XsT, const __bf16* __restrict__ GT,
+    float* __restrict__ partial,
+    int start, int m_pad, long long n_pad, int fa, int ncols_pad,
+    int gt_stride, int k_chunk)
+{
+    grad_partial_body<4>(XsT, GT, partial, start, m_pad, n_pad, fa,
+                         ncols_pad, gt_stride, k_chunk);
+}
+
+extern "C" __global__ __launch_bounds__(256) void k_grad_partial_96(
+    const __bf16* __restrict__ XsT, const __bf16* __restrict__ GT,
+    float* __restrict__ partial,
+    int start, int m_pad, long long n_pad, int fa, int ncols_pad,
+    int gt_stride, int k_chunk)
+{
+    grad_partial_body<3>(XsT, GT, partial, start, m_pad, n_pad, fa,
+                         ncols_pad, gt_stride, k_chunk);
 }
 
 // ---------------------------------------------------------------------- //
@@ -385,7 +495,7 @@ static hipError_t sgd_step_impl(
     const int m_pad = (int)((m + BM - 1) / BM) * BM;
     {
         dim3 grid(m_pad / BM, ncols_pad / BN);
-        size_t lds = (size_t)BN * LDC * 2 + 3072;
+        size_t lds = (size_t)BN * LDC * 2 + 3600;
         hipLaunchKernelGGL(k_fwd_gt, grid, dim3(256), lds, stream,
                            (const __bf16*)Xs, (const __bf16*)WbfT_in,
                            (__bf16*)GT, (const float*)y, (const int*)fold,
@@ -397,9 +507,17 @@ static hipError_t sgd_step_impl(
     }
     {
         const int k_chunk = (int)((m_pad / splitk + BK - 1) / BK) * BK;
-        dim3 grid((unsigned)(fa_store / BM), ncols_pad / BN, splitk);
+        // tile height: 96 where it pads fa with fewer rows than 128
+        const long long r96 = (fa + 95LL) / 96 * 96;
+        const long long r128 = (fa + 127LL) / 128 * 128;
+        const bool t96 = r96 < r128;
+        const long long rows = t96 ? r96 : r128;
+        if (rows > fa_store) return hipErrorInvalidValue;  // XsT rows read
+        dim3 grid((unsigned)(rows / (t96 ? 96 : 128)), ncols_pad / BN,
+                  splitk);
         size_t lds = 32768;
-        hipLaunchKernelGGL(k_grad_partial, grid, dim3(256), lds, stream,
+        hipLaunchKernelGGL(t96 ? k_grad_partial_96 : k_grad_partial, grid,
+                           dim3(256), lds, stream,
                            (const __bf16*)XsT, (const __bf16*)GT,
                            (float*)partial, (int)start, m_pad, n_pad, fa,
                            ncols_pad, gt_stride, k_chunk);

@@ -35,6 +35,12 @@ extern "C" hipError_t skdist_sgd_step_l1(
     float lr_scale, float momentum, int intercept_row,
     const void* col_l1, void* cpos, void* cneg,
     hipStream_t stream);
+// K2 alone; variant: 0 the launcher's rule, 1 / 2 the 128- / 96-row tile,
+// 3 the whole-fa kernel
+extern "C" hipError_t skdist_grad_partial(
+    const void* XsT, const void* GT, void* partial, long long start,
+    long long m, long long n_pad, long long fa_store, int fa, int ncols_pad,
+    int gt_stride, int splitk, int variant, hipStream_t stream);
 
 namespace {
 
@@ -190,6 +196,50 @@ void sgd_step(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
         (int)a.ncols_pad, (int)a.gt_stride, (int)a.splitk, (int)loss_id,
         (float)lr_scale, (float)momentum, (int)intercept_row, stream);
     TORCH_CHECK(err == hipSuccess, "skdist_sgd_step: ",
+                hipGetErrorString(err));
+}
+
+// K2 of one step on its own (tests, timing under a kernel trace): the
+// checks sgd_step makes on XsT, GT and partial, then one launch of the
+// kernel `variant` names
+void grad_partial(torch::Tensor XsT, torch::Tensor GT, torch::Tensor partial,
+                  int64_t start, int64_t m, int64_t variant) {
+    const auto bf16 = torch::kBFloat16;
+    check_t(XsT, bf16, "XsT");
+    check_t(GT, bf16, "GT");
+    check_t(partial, torch::kFloat32, "partial");
+    TORCH_CHECK(XsT.dim() == 2 && GT.dim() == 2, "XsT and GT must be 2-D");
+    TORCH_CHECK(partial.dim() == 3, "partial must be [splitk, fa, ncols_pad]");
+    const int64_t fa_store = XsT.size(0), n_pad = XsT.size(1);
+    const int64_t splitk = partial.size(0), fa = partial.size(1);
+    const int64_t ncols_pad = partial.size(2), gt_stride = GT.size(1);
+    TORCH_CHECK(fa >= 32 && fa % 32 == 0, "fa must be a multiple of 32");
+    TORCH_CHECK(n_pad >= 128 && n_pad % 128 == 0,
+                "n_pad must be a multiple of 128");
+    TORCH_CHECK(fa_store % 128 == 0, "fa_store must be a multiple of 128");
+    TORCH_CHECK(fa_store >= fa, "XsT must have at least fa rows");
+    TORCH_CHECK(ncols_pad >= 128 && ncols_pad % 128 == 0,
+                "ncols_pad must be a mult of 128");
+    TORCH_CHECK(splitk >= 1, "splitk must be >= 1");
+    TORCH_CHECK(m >= 1, "m must be >= 1");
+    const int64_t m_pad = (m + 127) / 128 * 128;
+    TORCH_CHECK(GT.size(0) == ncols_pad && gt_stride >= m_pad &&
+                gt_stride % 8 == 0,
+                "GT must be [ncols_pad, gt_stride >= ", m_pad,
+                "] with gt_stride a multiple of 8");
+    TORCH_CHECK(start >= 0 && start % 8 == 0,
+                "start must be a non-negative multiple of 8");
+    TORCH_CHECK(start + m_pad <= n_pad, "start + m_pad must be <= n_pad");
+    TORCH_CHECK(variant >= 0 && variant <= 3, "variant must be 0..3");
+    TORCH_CHECK(variant != 3 || fa <= 288,
+                "the whole-fa kernel takes fa <= 288");
+    TORCH_CHECK(variant != 2 || (fa + 95) / 96 * 96 <= fa_store,
+                "96-row tiles would read XsT rows past fa_store");
+    hipError_t err = skdist_grad_partial(
+        XsT.data_ptr(), GT.data_ptr(), partial.data_ptr(), start, m, n_pad,
+        fa_store, (int)fa, (int)ncols_pad, (int)gt_stride, (int)splitk,
+        (int)variant, c10::hip::getCurrentHIPStream().stream());
+    TORCH_CHECK(err == hipSuccess, "skdist_grad_partial: ",
                 hipGetErrorString(err));
 }
 
@@ -1250,6 +1300,9 @@ void hash_vectorize_utf8(torch::Tensor bytes, torch::Tensor doc_off,
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("sgd_step", &sgd_step, "fused batched SGD step (K1+K2+K3)");
     m.def("sgd_epoch", &sgd_epoch, "one epoch of fused SGD steps");
+    m.def("grad_partial", &grad_partial,
+          "K2 of one dense SGD step alone (variant: 0 rule, 1 128-row, "
+          "2 96-row, 3 whole-fa)");
     m.def("sp_sgd_epoch", &sp_sgd_epoch,
           "one epoch of the sparse text-scale solver");
     m.def("sgd_epoch_l1", &sgd_epoch_l1,

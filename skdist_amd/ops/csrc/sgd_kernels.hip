@@ -8,7 +8,8 @@
 //   K2 k_grad_partial:  partial[z] = Xᵀ·G  (split-K, deterministic slabs)
 //   K3 k_reduce_update: W -= lr * (Σz partial / m + λ∘W); refresh WbfT
 //
-// GEMM structure (K1/K2): 128×128 tile, 4 waves (2×2 of 64×64), MFMA bf16
+// GEMM structure (K1, K5 and K2's legacy tiles; K2's whole-fa kernel has
+// its own comment block): 128×128 tile, 4 waves (2×2 of 64×64), MFMA bf16
 // 16x16x32, BK=32, double-buffered LDS staged by global_load_lds_dwordx4
 // (wave-uniform LDS chunk base + lane×16B, per-lane swizzled SOURCE
 // address).  LDS image is lane-linear [128][32] bf16; the 16B slot of each
@@ -24,6 +25,8 @@
 //   GT    [ncols_pad][gts]   bf16
 //   partial [SPLITK][fa][ncols_pad] f32
 #include "common.h"
+
+#include <atomic>
 
 #define BM 128
 #define BN 128
@@ -249,15 +252,33 @@ extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt(
 
 // ---------------------------------------------------------------------- //
 // K2: Grad partial slabs, split-K over minibatch rows
-// grid: (ceil(fa/rows)*rows / rows, ncols_pad/BN, SPLITK), block 256
 //
-// The tile is rows x 128 with rows = 32 * MI: 2x2 waves, each holding MI
-// fragments of 16 feature rows by 4 of 16 columns.  MI = 4 is the 128-row
-// tile; MI = 3 is a 96-row tile for fa that 96 covers with fewer padded
-// rows (fa = 288: 3 x 96 against 3 x 128).  The A stage is then 6 chunks
-// of 16 rows (6 KiB) with the same XOR slot swizzle.  BK, the slab bounds
-// and the k order are those of the 128-row tile, so a partial element is
-// the same chain of MFMA accumulations under either.
+// partial[z][r][c] = sum over the slab's k of XsT[r][start + k] * GT[c][k],
+// slab z = [z * k_chunk, min(m_pad, (z + 1) * k_chunk)), accumulated by one
+// MFMA 16x16x32 per 32-deep k-step in ascending k.  Every kernel below
+// computes an element by that same chain, so which one ran cannot be told
+// from the result.
+//
+// fa <= K2F_MAX_FA (288): k_grad_partial_fullm, the whole-fa tile.
+//   grid (SPLITK, ncols_pad / K2F_BN), block 512.  One workgroup owns all
+//   fa feature rows of one column tile and one slab, so GT is fetched once
+//   per step.  The slab is the fast grid dimension: consecutive workgroups
+//   go to different XCDs, so with SPLITK = 8 an XCD sees one slab of XsT
+//   (fa x 1024 bf16, L2-resident) and its 24 column tiles.  8 waves as
+//   2 (rows) x 4 (columns); the 16-row fragments of the tile are dealt to
+//   the two wave rows alternately (fragment 2*mi + r), so both halves
+//   carry fa/32 fragments whatever fa is, and the kernel is instantiated
+//   per fa/32.  Both operands are staged by global_load_lds into a ring of
+//   K2F_NS stages of BK = 32; the loads of K2F_NS - 2 stages stay in flight
+//   across each raw s_barrier and are retired by a counted s_waitcnt vmcnt
+//   (see grad_partial_fullm_body).
+//
+// fa > K2F_MAX_FA: the legacy tiles, grid (ceil(fa/rows), ncols_pad/BN,
+//   SPLITK), block 256.  The tile is rows x 128 with rows = 32 * MI: 2x2
+//   waves, each holding MI fragments of 16 feature rows by 4 of 16 columns.
+//   MI = 4 is the 128-row tile; MI = 3 is a 96-row tile for fa that 96
+//   covers with fewer padded rows.  Double-buffered LDS, __syncthreads()
+//   per k-step.
 // ---------------------------------------------------------------------- //
 template <int MI>
 static __device__ __forceinline__ void grad_partial_body(
@@ -371,6 +392,252 @@ extern "C" __global__ __launch_bounds__(256) void k_grad_partial_96(
 {
     grad_partial_body<3>(XsT, GT, partial, start, m_pad, n_pad, fa,
                          ncols_pad, gt_stride, k_chunk);
+}
+
+// ---------------------------------------------------------------------- //
+// K2, whole-fa tile (fa <= K2F_MAX_FA).
+//
+// LDS, all in the one extern array: NS stages of [A: 18 chunks][B: BNT/16
+// chunks] followed by one spare chunk; a chunk is 16 rows x 32 k of bf16
+// (1 KiB), one global_load_lds_dwordx4 of one wave, in the XOR-swizzled
+// image frag_load reads.  MI = fa / 32 is a template parameter: only the
+// 2 * MI A chunks below fa are staged and multiplied, so XsT rows at or
+// past fa are never touched, and nothing in the loop is guarded.
+//
+// Staging: the chunks of a stage are dealt round-robin to the 8 waves,
+// chunk c = w + 8*s for slot s < G, G = ceil(chunks / 8).  A wave whose
+// last slot falls past the stage's chunks re-loads the first B chunk into
+// the spare chunk instead, so every wave issues exactly G loads per stage
+// and one vmcnt count is right for all of them.
+//
+// Ring: stage t lives in buffer t % NS and is issued D = NS - 1 steps
+// ahead.  Step t:
+//     s_waitcnt vmcnt(G * min(D - 1, T - 1 - t))   this wave's loads of
+//                                                  stage t have landed
+//     s_barrier        every wave's have, and every wave has finished
+//                      reading stage t - 1
+//     issue stage t + D into the buffer of stage t - 1
+//     fragments + MFMAs of stage t
+// so D - 1 stages stay in flight across the barrier; the count reaches 0
+// only in the last step of a slab.  No VGPR-destination global load is
+// issued anywhere in the kernel.
+// ---------------------------------------------------------------------- //
+#define K2F_MAX_FA 288
+#define K2F_A_BYTES (K2F_MAX_FA * BK * 2)
+
+static __device__ __forceinline__ void wait_vmcnt(int n) {
+    #define K2F_W(N) \
+        case N: asm volatile("s_waitcnt vmcnt(" #N ")" ::: "memory"); break;
+    switch (n) {
+    K2F_W(1) K2F_W(2) K2F_W(3) K2F_W(4) K2F_W(5) K2F_W(6) K2F_W(7) K2F_W(8)
+    K2F_W(9) K2F_W(10) K2F_W(11) K2F_W(12) K2F_W(13) K2F_W(14) K2F_W(15)
+    K2F_W(16)
+    default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
+    }
+    #undef K2F_W
+}
+
+template <int BNT, int NS, int MI>
+static __device__ __forceinline__ void grad_partial_fullm_body(
+    const __bf16* __restrict__ XsT,  // [fa_store][n_pad]
+    const __bf16* __restrict__ GT,   // [ncols_pad][gt_stride]
+    float* __restrict__ partial,     // [SPLITK][fa][ncols_pad]
+    int start, int m_pad, long long n_pad, int fa, int ncols_pad,
+    int gt_stride, int k_chunk)
+{
+    extern __shared__ __attribute__((aligned(16))) char sm[];
+    constexpr int NCB = BNT / 16;            // B chunks per stage
+    constexpr int NI = BNT / 64;             // column fragments per wave
+    constexpr int NCA = 2 * MI;              // A chunks (MI = fa / 32)
+    constexpr int STAGE = K2F_A_BYTES + NCB * 1024;
+    constexpr int SPARE = NS * STAGE;
+    constexpr int G = (NCA + NCB + 7) / 8;   // loads per wave per stage
+    constexpr int D = NS - 1;
+    static_assert(G * (D - 1) <= 16, "wait_vmcnt covers 0..16");
+
+    const int tid = threadIdx.x;
+    const int lane = tid & 63;
+    const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int z = blockIdx.x;   // slab first: see the K2 comment block
+    const int bn = blockIdx.y * BNT;
+
+    const int k0 = z * k_chunk;
+    const int k1 = min(m_pad, k0 + k_chunk);
+    const int T = (k1 > k0) ? (k1 - k0) / BK : 0;
+
+    // per slot: source of this lane's 16 B at k0, LDS offset of the chunk,
+    // and whether the offset moves with the stage (the spare does not)
+    const int lr = lane >> 2;
+    const int slot = (lane & 3) ^ ((lr >> 2) & 3);
+    const __bf16* src[G];
+    int dst[G], per_stage[G];
+    #pragma unroll
+    for (int s = 0; s < G; ++s) {
+        const int c = w + 8 * s;
+        if (c < NCA) {
+            src[s] = XsT + (long long)(16 * c + lr) * n_pad + start + k0 +
+                     slot * 8;
+            dst[s] = c * 1024;
+            per_stage[s] = STAGE;
+        } else {
+            const bool real = c < NCA + NCB;
+            const int cb = real ? c - NCA : 0;
+            src[s] = GT + (long long)(bn + 16 * cb + lr) * gt_stride + k0 +
+                     slot * 8;
+            dst[s] = real ? K2F_A_BYTES + cb * 1024 : SPARE;
+            per_stage[s] = real ? STAGE : 0;
+        }
+    }
+    #define K2F_ISSUE(buf, kt)                                              \
+        do {                                                                \
+            _Pragma("unroll") for (int s = 0; s < G; ++s)                   \
+                __builtin_amdgcn_global_load_lds(                           \
+                    (const unsigned int*)(src[s] + (kt) * BK),              \
+                    (unsigned int*)(sm + (buf) * per_stage[s] + dst[s]),    \
+                    16, 0, 0);                                              \
+        } while (0)
+
+    const int r = w >> 2;
+    const int wc = (w & 3) * (BNT / 4);
+    const int fr = lane & 15;
+    const int fk = (lane >> 4) * 8;
+
+    f32x4 acc[MI][NI] = {};
+    for (int t = 0; t < D && t < T; ++t) K2F_ISSUE(t, t);
+    int cur = 0;      // buffer of stage t
+    int nxt = D % NS; // buffer of stage t + D
+    for (int t = 0; t < T; ++t) {
+        wait_vmcnt(G * min(D - 1, T - 1 - t));
+        __builtin_amdgcn_s_barrier();
+        if (t + D < T) K2F_ISSUE(nxt, t + D);
+        const __bf16* A = (const __bf16*)(sm + cur * STAGE);
+        const __bf16* B = (const __bf16*)(sm + cur * STAGE + K2F_A_BYTES);
+        bf16x8 bfr[NI];
+        #pragma unroll
+        for (int ni = 0; ni < NI; ++ni)
+            bfr[ni] = frag_load(B, wc + ni * 16 + fr, fk);
+        bf16x8 af[MI];
+        #pragma unroll
+        for (int mi = 0; mi < MI; ++mi)
+            af[mi] = frag_load(A, (2 * mi + r) * 16 + fr, fk);
+        #pragma unroll
+        for (int mi = 0; mi < MI; ++mi)
+            #pragma unroll
+            for (int ni = 0; ni < NI; ++ni)
+                acc[mi][ni] =
+                    MFMA_BF16_16x16x32(af[mi], bfr[ni], acc[mi][ni]);
+        cur = (cur + 1 == NS) ? 0 : cur + 1;
+        nxt = (nxt + 1 == NS) ? 0 : nxt + 1;
+    }
+    #undef K2F_ISSUE
+
+    float* out = partial + (long long)z * fa * ncols_pad;
+    const int rw = lane >> 4;
+    #pragma unroll
+    for (int mi = 0; mi < MI; ++mi) {
+        const int rowb = (2 * mi + r) * 16 + rw * 4;
+        #pragma unroll
+        for (int ni = 0; ni < NI; ++ni) {
+            const int col = bn + wc + ni * 16 + fr;
+            #pragma unroll
+            for (int j = 0; j < 4; ++j)
+                out[(long long)(rowb + j) * ncols_pad + col] =
+                    acc[mi][ni][j];
+        }
+    }
+}
+
+#define K2F_BN 128
+#define K2F_NS 3
+#define K2F_LDS (K2F_NS * (K2F_A_BYTES + K2F_BN / 16 * 1024) + 1024)
+
+// one instantiation per fa / 32, chosen workgroup-uniformly.
+// __launch_bounds__(512): 103 VGPRs, no AGPRs, no scratch, 80896 B of LDS:
+// two workgroups fit a CU, and the flagship's grid (8 x 24 = 192) puts one
+// on each of 192 CUs, 2 waves per SIMD.
+extern "C" __global__ __launch_bounds__(512) void k_grad_partial_fullm(
+    const __bf16* __restrict__ XsT, const __bf16* __restrict__ GT,
+    float* __restrict__ partial,
+    int start, int m_pad, long long n_pad, int fa, int ncols_pad,
+    int gt_stride, int k_chunk)
+{
+    #define K2F_CASE(MI)                                                    \
+        case MI:                                                            \
+            grad_partial_fullm_body<K2F_BN, K2F_NS, MI>(                    \
+                XsT, GT, partial, start, m_pad, n_pad, fa, ncols_pad,       \
+                gt_stride, k_chunk);                                        \
+            break;
+    switch (fa >> 5) {
+    K2F_CASE(1) K2F_CASE(2) K2F_CASE(3) K2F_CASE(4) K2F_CASE(5)
+    K2F_CASE(6) K2F_CASE(7) K2F_CASE(8) K2F_CASE(9)
+    default: break;
+    }
+    #undef K2F_CASE
+}
+
+// ---------------------------------------------------------------------- //
+// K2 launcher.  variant 0 is the rule sgd_step uses: the whole-fa kernel
+// for fa <= K2F_MAX_FA, else the 96-row tile where it pads fa with fewer
+// rows than the 128-row tile.  1 / 2 / 3 force the 128-row tile, the
+// 96-row tile and the whole-fa kernel (tests, timing).
+// ---------------------------------------------------------------------- //
+static hipError_t launch_grad_partial(
+    const void* XsT, const void* GT, void* partial, int start, int m_pad,
+    long long n_pad, long long fa_store, int fa, int ncols_pad,
+    int gt_stride, int splitk, int variant, hipStream_t stream)
+{
+    const int k_chunk = (int)((m_pad / splitk + BK - 1) / BK) * BK;
+    const long long r96 = (fa + 95LL) / 96 * 96;
+    const long long r128 = (fa + 127LL) / 128 * 128;
+    if (variant == 0)
+        variant = fa <= K2F_MAX_FA ? 3 : (r96 < r128 ? 2 : 1);
+    if (variant == 3) {
+        if (fa > K2F_MAX_FA || fa > fa_store) return hipErrorInvalidValue;
+        const size_t lds = K2F_LDS;
+        // more than 64 KiB of dynamic LDS has to be allowed once per
+        // device; the first launch on a device is never a captured one
+        // (run_epochs_graphed runs epoch 0 eagerly)
+        static std::atomic<bool> allowed[64];
+        int dev = 0;
+        HIP_CHECK(hipGetDevice(&dev));
+        std::atomic<bool>& ok = allowed[dev & 63];
+        if (!ok.load(std::memory_order_acquire)) {
+            HIP_CHECK(hipFuncSetAttribute(
+                (const void*)k_grad_partial_fullm,
+                hipFuncAttributeMaxDynamicSharedMemorySize,
+                (int)lds));
+            ok.store(true, std::memory_order_release);
+        }
+        dim3 grid(splitk, ncols_pad / K2F_BN);
+        hipLaunchKernelGGL(k_grad_partial_fullm, grid, dim3(512), lds,
+                           stream,
+                           (const __bf16*)XsT, (const __bf16*)GT,
+                           (float*)partial, start, m_pad, n_pad, fa,
+                           ncols_pad, gt_stride, k_chunk);
+        return hipGetLastError();
+    }
+    if (variant != 1 && variant != 2) return hipErrorInvalidValue;
+    const bool t96 = variant == 2;
+    const long long rows = t96 ? r96 : r128;
+    if (rows > fa_store) return hipErrorInvalidValue;  // XsT rows read
+    dim3 grid((unsigned)(rows / (t96 ? 96 : 128)), ncols_pad / BN, splitk);
+    hipLaunchKernelGGL(t96 ? k_grad_partial_96 : k_grad_partial, grid,
+                       dim3(256), 32768, stream,
+                       (const __bf16*)XsT, (const __bf16*)GT,
+                       (float*)partial, start, m_pad, n_pad, fa, ncols_pad,
+                       gt_stride, k_chunk);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t skdist_grad_partial(
+    const void* XsT, const void* GT, void* partial, long long start,
+    long long m, long long n_pad, long long fa_store, int fa, int ncols_pad,
+    int gt_stride, int splitk, int variant, hipStream_t stream)
+{
+    const int m_pad = (int)((m + BM - 1) / BM) * BM;
+    return launch_grad_partial(XsT, GT, partial, (int)start, m_pad, n_pad,
+                               fa_store, fa, ncols_pad, gt_stride, splitk,
+                               variant, stream);
 }
 
 // ---------------------------------------------------------------------- //
@@ -505,24 +772,9 @@ static hipError_t sgd_step_impl(
                            loss_id);
         HIP_CHECK(hipGetLastError());
     }
-    {
-        const int k_chunk = (int)((m_pad / splitk + BK - 1) / BK) * BK;
-        // tile height: 96 where it pads fa with fewer rows than 128
-        const long long r96 = (fa + 95LL) / 96 * 96;
-        const long long r128 = (fa + 127LL) / 128 * 128;
-        const bool t96 = r96 < r128;
-        const long long rows = t96 ? r96 : r128;
-        if (rows > fa_store) return hipErrorInvalidValue;  // XsT rows read
-        dim3 grid((unsigned)(rows / (t96 ? 96 : 128)), ncols_pad / BN,
-                  splitk);
-        size_t lds = 32768;
-        hipLaunchKernelGGL(t96 ? k_grad_partial_96 : k_grad_partial, grid,
-                           dim3(256), lds, stream,
-                           (const __bf16*)XsT, (const __bf16*)GT,
-                           (float*)partial, (int)start, m_pad, n_pad, fa,
-                           ncols_pad, gt_stride, k_chunk);
-        HIP_CHECK(hipGetLastError());
-    }
+    HIP_CHECK(launch_grad_partial(XsT, GT, partial, (int)start, m_pad, n_pad,
+                                  fa_store, fa, ncols_pad, gt_stride, splitk,
+                                  0, stream));
     {
         dim3 grid(ncols_pad / 128, fa);
         if (col_l1 == nullptr) {

@@ -36,6 +36,8 @@ GEMM accumulation fp32 (MFMA native).  Gradient for column c:
 dloss: logistic  σ(z) - t
        hinge     -t' * 1[t'·z < 1]      (t' = 2t-1 ∈ {-1, +1})
        squared   z - t
+       softmax   softmax(z[i, group])[c] - t   (multinomial: the K columns
+                 of one model form a group, ``ColumnSpec.group_k``)
 """
 
 import os
@@ -43,8 +45,9 @@ import os
 import numpy as np
 import torch
 
-LOSS_LOG, LOSS_HINGE, LOSS_SQUARED = 0, 1, 2
-_LOSS_IDS = {"log": LOSS_LOG, "hinge": LOSS_HINGE, "squared": LOSS_SQUARED}
+LOSS_LOG, LOSS_HINGE, LOSS_SQUARED, LOSS_SOFTMAX = 0, 1, 2, 3
+_LOSS_IDS = {"log": LOSS_LOG, "hinge": LOSS_HINGE, "squared": LOSS_SQUARED,
+             "softmax": LOSS_SOFTMAX}
 
 
 def encode_labels(y_np):
@@ -335,10 +338,21 @@ class ColumnSpec:
     kernels); any positive entry routes the whole solve through the
     cumulative-penalty L1 variants, where columns with ``col_l1 == 0``
     still compute bit-for-bit what the L2-only solve computes.
+
+    ``group_k`` (optional, >= 2): the columns come in consecutive groups
+    of ``group_k``, one group per multinomial model (LOSS_SOFTMAX): the
+    columns of a group carry classes ``0..group_k-1`` in order, share one
+    ``col_fold`` and have no one-vs-one partner.  Checked here, on the
+    host, so neither solver path meets a malformed group.
     """
 
     def __init__(self, device, col_fold, col_class, col_lr, col_l2,
-                 col_class2=None, feat_mask=None, col_l1=None):
+                 col_class2=None, feat_mask=None, col_l1=None,
+                 group_k=None):
+        if group_k is not None:
+            group_k = _check_groups(group_k, col_fold, col_class,
+                                    col_class2)
+        self.group_k = group_k
         as_t = lambda a, dt: torch.as_tensor(
             np.ascontiguousarray(a), dtype=dt, device=device
         )
@@ -361,6 +375,39 @@ class ColumnSpec:
         self.col_l1 = col_l1
 
 
+def _check_groups(group_k, col_fold, col_class, col_class2):
+    """Validate the multinomial column groups of a ColumnSpec."""
+    if (isinstance(group_k, bool)
+            or not isinstance(group_k, (int, np.integer)) or group_k < 2):
+        raise ValueError(f"group_k must be an integer >= 2, got {group_k!r}")
+    gk = int(group_k)
+    fold = np.asarray(col_fold)
+    cls = np.asarray(col_class)
+    if len(fold) == 0 or len(fold) % gk or len(cls) != len(fold):
+        raise ValueError(
+            f"group_k={gk} needs a positive multiple of {gk} columns, "
+            f"got {len(fold)}")
+    if not (cls.reshape(-1, gk) == np.arange(gk)[None, :]).all():
+        raise ValueError(
+            f"every group of {gk} columns must carry col_class 0..{gk - 1} "
+            "in order")
+    f2 = fold.reshape(-1, gk)
+    if not (f2 == f2[:, :1]).all():
+        raise ValueError("the columns of a group must share one col_fold")
+    if col_class2 is not None and (np.asarray(col_class2) != -1).any():
+        raise ValueError("grouped columns cannot be one-vs-one columns")
+    return gk
+
+
+def _check_loss_groups(spec, loss_id):
+    """The softmax loss needs column groups; no other loss takes them."""
+    gk = getattr(spec, "group_k", None)
+    if loss_id == LOSS_SOFTMAX and gk is None:
+        raise ValueError("the softmax loss needs ColumnSpec(group_k=...)")
+    if loss_id != LOSS_SOFTMAX and gk is not None:
+        raise ValueError("ColumnSpec.group_k is for the softmax loss only")
+
+
 def batched_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
                     momentum=0.0, lr_decay=0.0, force_eager=False,
                     adaptive=None):
@@ -370,7 +417,13 @@ def batched_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
     the host RNG, applied as a device gather); batch composition stays
     fixed across epochs, matching the HIP path (hip_sgd_solve).
     """
+    loss_id = _LOSS_IDS[loss] if isinstance(loss, str) else loss
+    _check_loss_groups(spec, loss_id)
     if getattr(ds, "is_sparse", False):
+        if loss_id == LOSS_SOFTMAX:
+            raise ValueError(
+                "multi_class='multinomial' is not supported on the "
+                "sparse-native solver yet")
         from ._sparse_sgd import sparse_sgd_fit
 
         return sparse_sgd_fit(ds, spec, loss, epochs, batch_size,
@@ -379,7 +432,6 @@ def batched_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
                               adaptive=adaptive)
     device = ds.device
     n, fa = ds.Xaug.shape
-    loss_id = _LOSS_IDS[loss] if isinstance(loss, str) else loss
     hip = (not force_eager) and _use_hip(device)
     if hip:
         from ..ops import hip_sgd_solve
@@ -477,7 +529,11 @@ def _sgd_step_torch(Xaug, y_float, fold_id, idx, W, V, spec, loss_id,
     if loss_id == LOSS_SQUARED and spec.col_class[0].item() < 0:
         t = yb.unsqueeze(1).expand_as(Z)
 
-    if loss_id == LOSS_LOG:
+    if loss_id == LOSS_SOFTMAX:
+        gk = spec.group_k
+        G = (torch.softmax(Z.view(m, -1, gk), dim=2)
+             - t.view(m, -1, gk)).reshape(m, -1)
+    elif loss_id == LOSS_LOG:
         G = torch.sigmoid(Z) - t
     elif loss_id == LOSS_HINGE:
         s = 2.0 * t - 1.0

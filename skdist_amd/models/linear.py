@@ -21,6 +21,7 @@ from sklearn.base import BaseEstimator, ClassifierMixin, RegressorMixin
 from ._sgd import (
     LOSS_HINGE,
     LOSS_LOG,
+    LOSS_SOFTMAX,
     LOSS_SQUARED,
     ColumnSpec,
     DeviceDataset,
@@ -133,6 +134,16 @@ class _BatchedLinearBase(BaseEstimator):
              "l1_ratio": getattr(self, "l1_ratio", None)},
             n_train)
 
+    def _solve_loss(self, n_classes):
+        """(loss, group width) of this estimator's batched solve: the
+        softmax loss over groups of ``n_classes`` columns for a
+        multinomial fit of 3 or more classes, else the estimator's own
+        per-column loss and no groups (2 classes are one sigmoid column
+        under either setting).  Validates ``multi_class``."""
+        if _multi_class(self) == "multinomial" and n_classes >= 3:
+            return LOSS_SOFTMAX, int(n_classes)
+        return self._loss, None
+
     def _hyper_names(self):
         if hasattr(self, "C"):
             return {"C", "penalty", "l1_ratio"}
@@ -180,8 +191,10 @@ class _BatchedLinearBase(BaseEstimator):
                 else np.arange(k, dtype=np.int32)
             )
         else:
+            k = 0
             ncols = 1
             col_class = np.array([-1], dtype=np.int32)
+        loss, group_k = self._solve_loss(k)
         l2, l1 = self._lam(ds.n)
         spec = ColumnSpec(
             ds.device,
@@ -190,9 +203,10 @@ class _BatchedLinearBase(BaseEstimator):
             col_lr=np.full(ncols, self.lr, dtype=np.float32),
             col_l2=np.full(ncols, l2, dtype=np.float32),
             col_l1=np.full(ncols, l1, dtype=np.float32),
+            group_k=group_k,
         )
         W = batched_sgd_fit(
-            ds, spec, self._loss, self.epochs, self.batch_size,
+            ds, spec, loss, self.epochs, self.batch_size,
             seed=self._seed(), momentum=self.momentum,
             lr_decay=getattr(self, "lr_decay", 0.0),
             adaptive=getattr(self, "adaptive", None),
@@ -345,6 +359,9 @@ class _BatchedLinearBase(BaseEstimator):
             n_classes = 2
             cols_per_model = 1
             cls = np.array([-1], dtype=np.int32)
+        # one solve has one loss: multi_class is no batchable grid key
+        # (rejected above), so the base estimator's setting holds
+        loss, group_k = self._solve_loss(n_classes if is_clf else 0)
 
         # this rank's shard of candidates
         cand_ids = (
@@ -400,9 +417,10 @@ class _BatchedLinearBase(BaseEstimator):
                 col_lr=np.asarray(col_lr, dtype=np.float32),
                 col_l2=np.asarray(col_l2, dtype=np.float32),
                 col_l1=np.asarray(col_l1, dtype=np.float32),
+                group_k=group_k,
             )
             W = batched_sgd_fit(
-                ds, spec, self._loss, self.epochs, self.batch_size,
+                ds, spec, loss, self.epochs, self.batch_size,
                 seed=self._seed(), momentum=self.momentum,
                 lr_decay=getattr(self, "lr_decay", 0.0),
                 adaptive=getattr(self, "adaptive", None),
@@ -514,6 +532,7 @@ class _BatchedLinearBase(BaseEstimator):
             n_classes = 2
             cls = np.array([-1], dtype=np.int32)
         cpm = len(cls)
+        loss, group_k = self._solve_loss(n_classes if is_clf else 0)
 
         set_ids = (
             cluster.shard_indices(n_sets) if cluster is not None
@@ -559,9 +578,10 @@ class _BatchedLinearBase(BaseEstimator):
                 col_l2=np.asarray(col_l2, dtype=np.float32),
                 feat_mask=feat_mask,
                 col_l1=np.asarray(col_l1, dtype=np.float32),
+                group_k=group_k,
             )
             W = batched_sgd_fit(
-                ds, spec, self._loss, self.epochs, self.batch_size,
+                ds, spec, loss, self.epochs, self.batch_size,
                 seed=self._seed(), momentum=self.momentum,
                 lr_decay=getattr(self, "lr_decay", 0.0),
                 adaptive=getattr(self, "adaptive", None),
@@ -773,6 +793,8 @@ class _BatchedLinearBase(BaseEstimator):
             if scores.ndim == 1:
                 p = 1.0 / (1.0 + np.exp(-scores))
                 return np.column_stack([1.0 - p, p])
+            if _multi_class(self) == "multinomial":
+                return _softmax_rows(scores)
             p = 1.0 / (1.0 + np.exp(-scores))
             p /= p.sum(axis=1, keepdims=True)
             return p
@@ -824,6 +846,25 @@ class _BatchedLinearBase(BaseEstimator):
 
 
 _PENALTIES = ("l2", "l1", "elasticnet")
+_MULTI_CLASS = ("ovr", "multinomial")
+
+
+def _multi_class(est):
+    """Validated ``multi_class`` of an estimator; ``"ovr"`` for one
+    without the parameter (LinearSVC, Ridge, and a LogisticRegression
+    pickled before it existed)."""
+    mc = getattr(est, "multi_class", "ovr")
+    if not isinstance(mc, str) or mc not in _MULTI_CLASS:
+        raise ValueError(
+            f"multi_class must be one of {_MULTI_CLASS}, got {mc!r}")
+    return mc
+
+
+def _softmax_rows(scores):
+    """Row-wise softmax of [n, K] decision values, max-shifted."""
+    e = np.exp(scores - scores.max(axis=1, keepdims=True))
+    e /= e.sum(axis=1, keepdims=True)
+    return e
 
 
 def _l1_share(params):
@@ -873,7 +914,22 @@ def sk_clone_without_sc(est):
 
 
 class LogisticRegression(ClassifierMixin, _BatchedLinearBase):
-    """Batched-SGD logistic regression (binary + internal one-vs-rest).
+    """Batched-SGD logistic regression: binary, one-vs-rest or multinomial.
+
+    ``multi_class="ovr"`` (the default -- a deliberate deviation from
+    sklearn, whose default is the multinomial model) trains one
+    independent sigmoid column per class and ``predict_proba`` returns
+    the row-normalised sigmoids.  ``multi_class="multinomial"`` trains
+    the K columns of a model jointly on the softmax cross-entropy
+    (sklearn's model, same ``lam = 1 / (C n)``) and ``predict_proba`` is
+    the softmax of ``decision_function``.  With 2 classes both settings
+    are the same single sigmoid column, bit for bit.  Multinomial fits
+    compose with ``penalty``, ``class_weight``, ``sample_weight``,
+    ``momentum`` and ``lr_decay``, batch into one search solve (a
+    ``multi_class`` key in a parameter grid does not: one solve has one
+    loss, so such a grid takes the generic path), take at most 128
+    classes on the GPU, and are not available on the sparse-native
+    solver yet.
 
     The solver differs from sklearn's lbfgs/liblinear (SURVEY.md §7 "exact
     sklearn numerics"): features are standardized internally (coefficients
@@ -901,10 +957,11 @@ class LogisticRegression(ClassifierMixin, _BatchedLinearBase):
     def __init__(self, C=1.0, lr=0.5, epochs=20, batch_size=8192,
                  momentum=0.9, lr_decay=0.0, standardize=True,
                  class_weight=None, random_state=None, adaptive=None,
-                 sc=None, penalty="l2", l1_ratio=None):
+                 sc=None, penalty="l2", l1_ratio=None, multi_class="ovr"):
         self.C = C
         self.penalty = penalty
         self.l1_ratio = l1_ratio
+        self.multi_class = multi_class
         self.adaptive = adaptive
         self.class_weight = class_weight
         self.lr_decay = lr_decay
@@ -921,6 +978,8 @@ class LogisticRegression(ClassifierMixin, _BatchedLinearBase):
         if scores.ndim == 1:
             p = 1.0 / (1.0 + np.exp(-scores))
             return np.column_stack([1.0 - p, p])
+        if _multi_class(self) == "multinomial":
+            return _softmax_rows(scores)
         p = 1.0 / (1.0 + np.exp(-scores))
         p /= p.sum(axis=1, keepdims=True)
         return p

@@ -174,6 +174,31 @@ def _pad_cols(t, ncols_pad, fill):
     return out.contiguous()
 
 
+SOFTMAX_LOSS_ID = 3       # models/_sgd.py LOSS_SOFTMAX, csrc/common.h
+SOFTMAX_MAX_CLASSES = 128  # one group must fit a 128-column kernel tile
+
+
+def softmax_columns(n_models, gk):
+    """Kernel column of every (model, class) of a multinomial solve, and
+    the padded column count.
+
+    k_fwd_gt_softmax reduces over the ``gk`` columns of a model inside
+    one 128-column tile, so a group never straddles a tile: a tile holds
+    ``gpt = 128 // gk`` groups in its first ``gpt * gk`` columns and the
+    rest of the tile is dead (``128 % gk`` columns: none for gk = 64,
+    2 for gk = 3, 63 for gk = 65).  Model j, class c lives at column
+    ``(j // gpt) * 128 + (j % gpt) * gk + c``.
+    """
+    import numpy as np
+
+    gpt = 128 // gk
+    j = np.arange(n_models)
+    base = (j // gpt) * 128 + (j % gpt) * gk
+    cols = (base[:, None] + np.arange(gk)[None, :]).ravel()
+    ncp = (n_models + gpt - 1) // gpt * 128
+    return cols, ncp
+
+
 def hip_sgd_solve(ds, spec, loss_id, epochs, batch_size, seed, momentum,
                   lr_decay, splitk=8):
     """Full batched SGD solve on the HIP kernels (K1+K2+K3 per step).
@@ -186,6 +211,11 @@ def hip_sgd_solve(ds, spec, loss_id, epochs, batch_size, seed, momentum,
     k_reduce_update_l1 through the ``*_l1`` entries; it costs two more
     [fa, ncols_pad] fp32 tables (the per-weight L1 credits).  Without it
     the calls below are the L2-only ones, unchanged.
+
+    The softmax loss (``spec.group_k`` set) spreads the columns into the
+    tile layout of ``softmax_columns`` -- dead columns are pad columns --
+    and gathers W back, so the caller sees compact model-major columns
+    like for every other loss.
     """
     import numpy as np
 
@@ -195,6 +225,26 @@ def hip_sgd_solve(ds, spec, loss_id, epochs, batch_size, seed, momentum,
     assert fa % 32 == 0
     ncols = spec.ncols
     ncp = (ncols + 127) // 128 * 128
+    gk = getattr(spec, "group_k", None)
+    if (int(loss_id) == SOFTMAX_LOSS_ID) != (gk is not None):
+        raise ValueError(
+            "the softmax loss and ColumnSpec.group_k go together")
+    place = None    # kernel column of each spec column (softmax only)
+    if gk is not None:
+        if gk > SOFTMAX_MAX_CLASSES:
+            raise ValueError(
+                f"multi_class='multinomial' on the HIP path takes at most "
+                f"{SOFTMAX_MAX_CLASSES} classes, got {gk}")
+        cols_np, ncp = softmax_columns(ncols // gk, gk)
+        place = torch.as_tensor(cols_np, dtype=torch.int64, device=device)
+    gk_arg = int(gk) if gk is not None else 0
+
+    def pad_cols(t, fill):
+        if place is None:
+            return _pad_cols(t, ncp, fill)
+        out = torch.full((ncp,), fill, dtype=t.dtype, device=t.device)
+        out[place] = t
+        return out.contiguous()
     bs = min(batch_size, (n + 127) // 128 * 128)
     bs = max(128, bs - bs % 128)
     gts = (bs + 127) // 128 * 128
@@ -208,14 +258,17 @@ def hip_sgd_solve(ds, spec, loss_id, epochs, batch_size, seed, momentum,
     GT = torch.empty(ncp, gts, dtype=torch.bfloat16, device=device)
     partial = torch.empty(splitk, fa, ncp, dtype=torch.float32,
                           device=device)
-    cls_p = _pad_cols(spec.col_class, ncp, -99)
-    cfold_p = _pad_cols(spec.col_fold, ncp, -9)
-    cls2_p = _pad_cols(spec.col_class2, ncp, -1)
-    lr_p = _pad_cols(spec.col_lr, ncp, 0.0)
-    l2_p = _pad_cols(spec.col_l2, ncp, 0.0)
+    cls_p = pad_cols(spec.col_class, -99)
+    cfold_p = pad_cols(spec.col_fold, -9)
+    cls2_p = pad_cols(spec.col_class2, -1)
+    lr_p = pad_cols(spec.col_lr, 0.0)
+    l2_p = pad_cols(spec.col_l2, 0.0)
     if getattr(spec, "feat_mask", None) is not None:
         fmask = torch.ones(fa, ncp, dtype=torch.uint8, device=device)
-        fmask[:, :ncols] = spec.feat_mask
+        if place is None:
+            fmask[:, :ncols] = spec.feat_mask
+        else:
+            fmask[:, place] = spec.feat_mask
         fmask = fmask.contiguous()
     else:
         fmask = torch.empty(0, dtype=torch.uint8, device=device)
@@ -243,7 +296,7 @@ def hip_sgd_solve(ds, spec, loss_id, epochs, batch_size, seed, momentum,
     if col_l1 is not None:
         if not 0.0 <= momentum < 1.0:
             raise ValueError("the L1 update needs momentum in [0, 1)")
-        l1_p = _pad_cols(col_l1, ncp, 0.0)
+        l1_p = pad_cols(col_l1, 0.0)
         cpos = torch.zeros_like(W)
         cneg = torch.zeros_like(W)
         if lr_decay == 0.0:
@@ -251,7 +304,7 @@ def hip_sgd_solve(ds, spec, loss_id, epochs, batch_size, seed, momentum,
                 Xs, XsT, GT, W, V, WbfT, partial, ys, folds,
                 cls_p, cfold_p, cls2_p, lr_p, l2_p, fmask, rw_t, inv_m,
                 bs, int(loss_id), float(momentum), int(ds.intercept_row),
-                int(epochs), l1_p, cpos, cneg,
+                int(epochs), l1_p, cpos, cneg, gk_arg,
             )
         else:
             for epoch in range(epochs):
@@ -261,7 +314,7 @@ def hip_sgd_solve(ds, spec, loss_id, epochs, batch_size, seed, momentum,
                     cls_p, cfold_p, cls2_p, lr_p, l2_p, fmask, rw_t,
                     inv_m, bs, int(loss_id), float(lr_scale),
                     float(momentum), int(ds.intercept_row),
-                    l1_p, cpos, cneg,
+                    l1_p, cpos, cneg, gk_arg,
                 )
     elif lr_decay == 0.0:
         # constant lr_scale: every epoch launches the identical
@@ -270,7 +323,7 @@ def hip_sgd_solve(ds, spec, loss_id, epochs, batch_size, seed, momentum,
             Xs, XsT, GT, W, V, WbfT, partial, ys, folds,
             cls_p, cfold_p, cls2_p, lr_p, l2_p, fmask, rw_t, inv_m,
             bs, int(loss_id), float(momentum), int(ds.intercept_row),
-            int(epochs),
+            int(epochs), gk_arg,
         )
     else:
         for epoch in range(epochs):
@@ -279,6 +332,8 @@ def hip_sgd_solve(ds, spec, loss_id, epochs, batch_size, seed, momentum,
                 Xs, XsT, GT, W, V, WbfT, partial, ys, folds,
                 cls_p, cfold_p, cls2_p, lr_p, l2_p, fmask, rw_t, inv_m,
                 bs, int(loss_id), float(lr_scale), float(momentum),
-                int(ds.intercept_row),
+                int(ds.intercept_row), gk_arg,
             )
+    if place is not None:
+        return W.index_select(1, place)
     return W[:, :ncols]

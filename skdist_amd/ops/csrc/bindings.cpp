@@ -19,7 +19,7 @@ extern "C" hipError_t skdist_sgd_step(
     long long start, long long m, long long n, long long n_pad,
     long long fa_store, int fa, int ncols_pad,
     int gt_stride, int splitk, int loss_id,
-    float lr_scale, float momentum, int intercept_row,
+    float lr_scale, float momentum, int intercept_row, int group_k,
     hipStream_t stream);
 // same step with the cumulative-penalty L1 update (k_reduce_update_l1)
 extern "C" hipError_t skdist_sgd_step_l1(
@@ -33,7 +33,7 @@ extern "C" hipError_t skdist_sgd_step_l1(
     long long fa_store, int fa, int ncols_pad,
     int gt_stride, int splitk, int loss_id,
     float lr_scale, float momentum, int intercept_row,
-    const void* col_l1, void* cpos, void* cneg,
+    const void* col_l1, void* cpos, void* cneg, int group_k,
     hipStream_t stream);
 // K2 alone; variant: 0 the launcher's rule, 1 / 2 the 128- / 96-row tile,
 // 3 the whole-fa kernel
@@ -78,6 +78,8 @@ struct StepArgs {
 // kernels index: shared by sgd_step and the epoch / solve entries with and
 // without L1.  `rows` is the largest row count one step covers (m for
 // sgd_step, the batch size otherwise); V, fmask and row_w may be empty.
+// loss_id 3 (softmax) trains groups of group_k columns (2..128) with
+// k_fwd_gt_softmax; every other loss takes group_k == 0.
 StepArgs check_step_tensors(
     const torch::Tensor& Xs, const torch::Tensor& XsT,
     const torch::Tensor& GT, const torch::Tensor& W, const torch::Tensor& V,
@@ -87,7 +89,16 @@ StepArgs check_step_tensors(
     const torch::Tensor& col_class2, const torch::Tensor& col_lr,
     const torch::Tensor& col_l2, const torch::Tensor& fmask,
     const torch::Tensor& row_w, int64_t rows, double momentum,
-    int64_t intercept_row) {
+    int64_t intercept_row, int64_t loss_id, int64_t group_k) {
+    TORCH_CHECK(loss_id >= 0 && loss_id <= 3, "loss_id must be 0..3");
+    if (loss_id == 3) {
+        TORCH_CHECK(group_k >= 2 && group_k <= 128,
+                    "the softmax loss needs group_k in [2, 128], got ",
+                    group_k);
+    } else {
+        TORCH_CHECK(group_k == 0,
+                    "group_k is for the softmax loss (loss_id 3) only");
+    }
     const auto bf16 = torch::kBFloat16;
     const auto f32 = torch::kFloat32;
     const auto i32 = torch::kInt32;
@@ -171,12 +182,13 @@ void sgd_step(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
               torch::Tensor col_lr, torch::Tensor col_l2,
               torch::Tensor fmask, torch::Tensor row_w,
               int64_t start, int64_t m, int64_t loss_id, double lr_scale,
-              double momentum, int64_t intercept_row, double inv_m) {
+              double momentum, int64_t intercept_row, double inv_m,
+              int64_t group_k) {
     TORCH_CHECK(m >= 1, "m must be >= 1");
     auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
                                 col_class, col_fold, col_class2, col_lr,
                                 col_l2, fmask, row_w, m, momentum,
-                                intercept_row);
+                                intercept_row, loss_id, group_k);
     // K2 stages 16 B chunks of XsT from column `start` on
     TORCH_CHECK(start >= 0 && start % 8 == 0,
                 "start must be a non-negative multiple of 8");
@@ -194,7 +206,8 @@ void sgd_step(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
         row_w.numel() ? row_w.data_ptr() : nullptr, (float)inv_m,
         start, m, a.n, a.n_pad, a.fa_store, (int)a.fa,
         (int)a.ncols_pad, (int)a.gt_stride, (int)a.splitk, (int)loss_id,
-        (float)lr_scale, (float)momentum, (int)intercept_row, stream);
+        (float)lr_scale, (float)momentum, (int)intercept_row, (int)group_k,
+        stream);
     TORCH_CHECK(err == hipSuccess, "skdist_sgd_step: ",
                 hipGetErrorString(err));
 }
@@ -343,7 +356,8 @@ void enqueue_epoch(const StepArgs& a, torch::Tensor& Xs, torch::Tensor& XsT,
                    torch::Tensor& row_w, const float* inv_p,
                    int64_t batch_size, int64_t loss_id, float lr_scale,
                    double momentum, int64_t intercept_row,
-                   const L1Args& l1, hipStream_t st, const char* who) {
+                   const L1Args& l1, int64_t group_k, hipStream_t st,
+                   const char* who) {
     const bool has_V = V.numel() > 0;
     int64_t bi = 0;
     for (int64_t start = 0; start < a.n; start += batch_size, ++bi) {
@@ -363,7 +377,7 @@ void enqueue_epoch(const StepArgs& a, torch::Tensor& Xs, torch::Tensor& XsT,
                 start, m, a.n, a.n_pad, a.fa_store,
                 (int)a.fa, (int)a.ncols_pad, (int)a.gt_stride,
                 (int)a.splitk, (int)loss_id, lr_scale, (float)momentum,
-                (int)intercept_row, st);
+                (int)intercept_row, (int)group_k, st);
         } else {
             err = skdist_sgd_step_l1(
                 Xs.data_ptr(), XsT.data_ptr(), WbfT.data_ptr(),
@@ -375,7 +389,8 @@ void enqueue_epoch(const StepArgs& a, torch::Tensor& Xs, torch::Tensor& XsT,
                 start, m, a.n, a.n_pad, a.fa_store,
                 (int)a.fa, (int)a.ncols_pad, (int)a.gt_stride,
                 (int)a.splitk, (int)loss_id, lr_scale, (float)momentum,
-                (int)intercept_row, l1.col_l1, l1.cpos, l1.cneg, st);
+                (int)intercept_row, l1.col_l1, l1.cpos, l1.cneg,
+                (int)group_k, st);
         }
         TORCH_CHECK(err == hipSuccess, who, ": ", hipGetErrorString(err));
     }
@@ -392,17 +407,18 @@ void sgd_epoch(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                torch::Tensor fmask, torch::Tensor row_w,
                torch::Tensor inv_m_cpu,  // [n_batches] f32 on CPU
                int64_t batch_size, int64_t loss_id, double lr_scale,
-               double momentum, int64_t intercept_row) {
+               double momentum, int64_t intercept_row, int64_t group_k) {
     auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
                                 col_class, col_fold, col_class2, col_lr,
                                 col_l2, fmask, row_w, batch_size, momentum,
-                                intercept_row);
+                                intercept_row, loss_id, group_k);
     check_batches(a, batch_size, inv_m_cpu);
     enqueue_epoch(a, Xs, XsT, GT, W, V, WbfT, partial, y, fold, col_class,
                   col_fold, col_class2, col_lr, col_l2, fmask, row_w,
                   (const float*)inv_m_cpu.data_ptr(), batch_size, loss_id,
                   (float)lr_scale, momentum, intercept_row, L1Args{},
-                  c10::hip::getCurrentHIPStream().stream(), "sgd_epoch");
+                  group_k, c10::hip::getCurrentHIPStream().stream(),
+                  "sgd_epoch");
 }
 
 // all epochs in one call; lr_scale is constant (lr_decay=0), so every
@@ -416,11 +432,11 @@ void sgd_solve(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                torch::Tensor fmask, torch::Tensor row_w,
                torch::Tensor inv_m_cpu, int64_t batch_size,
                int64_t loss_id, double momentum, int64_t intercept_row,
-               int64_t epochs) {
+               int64_t epochs, int64_t group_k) {
     auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
                                 col_class, col_fold, col_class2, col_lr,
                                 col_l2, fmask, row_w, batch_size, momentum,
-                                intercept_row);
+                                intercept_row, loss_id, group_k);
     check_batches(a, batch_size, inv_m_cpu);
     const float* inv_p = (const float*)inv_m_cpu.data_ptr();
     auto torch_stream = c10::hip::getCurrentHIPStream().stream();
@@ -428,7 +444,8 @@ void sgd_solve(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
         enqueue_epoch(a, Xs, XsT, GT, W, V, WbfT, partial, y, fold,
                       col_class, col_fold, col_class2, col_lr, col_l2,
                       fmask, row_w, inv_p, batch_size, loss_id, 1.0f,
-                      momentum, intercept_row, L1Args{}, st, "sgd_solve");
+                      momentum, intercept_row, L1Args{}, group_k, st,
+                      "sgd_solve");
     };
     run_epochs_graphed(epochs, torch_stream, body);
 }
@@ -446,17 +463,18 @@ void sgd_epoch_l1(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                   torch::Tensor inv_m_cpu, int64_t batch_size,
                   int64_t loss_id, double lr_scale, double momentum,
                   int64_t intercept_row, torch::Tensor col_l1,
-                  torch::Tensor cpos, torch::Tensor cneg) {
+                  torch::Tensor cpos, torch::Tensor cneg,
+                  int64_t group_k) {
     auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
                                 col_class, col_fold, col_class2, col_lr,
                                 col_l2, fmask, row_w, batch_size, momentum,
-                                intercept_row);
+                                intercept_row, loss_id, group_k);
     check_batches(a, batch_size, inv_m_cpu);
     auto l1 = check_l1(col_l1, cpos, cneg, W, momentum);
     enqueue_epoch(a, Xs, XsT, GT, W, V, WbfT, partial, y, fold, col_class,
                   col_fold, col_class2, col_lr, col_l2, fmask, row_w,
                   (const float*)inv_m_cpu.data_ptr(), batch_size, loss_id,
-                  (float)lr_scale, momentum, intercept_row, l1,
+                  (float)lr_scale, momentum, intercept_row, l1, group_k,
                   c10::hip::getCurrentHIPStream().stream(), "sgd_epoch_l1");
 }
 
@@ -470,11 +488,11 @@ void sgd_solve_l1(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                   torch::Tensor inv_m_cpu, int64_t batch_size,
                   int64_t loss_id, double momentum, int64_t intercept_row,
                   int64_t epochs, torch::Tensor col_l1, torch::Tensor cpos,
-                  torch::Tensor cneg) {
+                  torch::Tensor cneg, int64_t group_k) {
     auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
                                 col_class, col_fold, col_class2, col_lr,
                                 col_l2, fmask, row_w, batch_size, momentum,
-                                intercept_row);
+                                intercept_row, loss_id, group_k);
     check_batches(a, batch_size, inv_m_cpu);
     auto l1 = check_l1(col_l1, cpos, cneg, W, momentum);
     const float* inv_p = (const float*)inv_m_cpu.data_ptr();
@@ -483,7 +501,8 @@ void sgd_solve_l1(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
         enqueue_epoch(a, Xs, XsT, GT, W, V, WbfT, partial, y, fold,
                       col_class, col_fold, col_class2, col_lr, col_l2,
                       fmask, row_w, inv_p, batch_size, loss_id, 1.0f,
-                      momentum, intercept_row, l1, st, "sgd_solve_l1");
+                      momentum, intercept_row, l1, group_k, st,
+                      "sgd_solve_l1");
     };
     run_epochs_graphed(epochs, torch_stream, body);
 }
@@ -1298,19 +1317,47 @@ void hash_vectorize_utf8(torch::Tensor bytes, torch::Tensor doc_off,
 }  // namespace
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
-    m.def("sgd_step", &sgd_step, "fused batched SGD step (K1+K2+K3)");
-    m.def("sgd_epoch", &sgd_epoch, "one epoch of fused SGD steps");
+    // the tensors every dense step entry takes first, in order; naming
+    // the arguments lets the trailing group_k (softmax group width)
+    // default to 0, so positional calls without it keep working
+    #define STEP_TENSORS                                                    \
+        py::arg("Xs"), py::arg("XsT"), py::arg("GT"), py::arg("W"),         \
+        py::arg("V"), py::arg("WbfT"), py::arg("partial"), py::arg("y"),    \
+        py::arg("fold"), py::arg("col_class"), py::arg("col_fold"),         \
+        py::arg("col_class2"), py::arg("col_lr"), py::arg("col_l2"),        \
+        py::arg("fmask"), py::arg("row_w")
+    m.def("sgd_step", &sgd_step, "fused batched SGD step (K1+K2+K3)",
+          STEP_TENSORS, py::arg("start"), py::arg("m"), py::arg("loss_id"),
+          py::arg("lr_scale"), py::arg("momentum"),
+          py::arg("intercept_row"), py::arg("inv_m"),
+          py::arg("group_k") = 0);
+    m.def("sgd_epoch", &sgd_epoch, "one epoch of fused SGD steps",
+          STEP_TENSORS, py::arg("inv_m"), py::arg("batch_size"),
+          py::arg("loss_id"), py::arg("lr_scale"), py::arg("momentum"),
+          py::arg("intercept_row"), py::arg("group_k") = 0);
     m.def("grad_partial", &grad_partial,
           "K2 of one dense SGD step alone (variant: 0 rule, 1 128-row, "
           "2 96-row, 3 whole-fa)");
     m.def("sp_sgd_epoch", &sp_sgd_epoch,
           "one epoch of the sparse text-scale solver");
     m.def("sgd_epoch_l1", &sgd_epoch_l1,
-          "one epoch of fused SGD steps with the L1 update");
+          "one epoch of fused SGD steps with the L1 update",
+          STEP_TENSORS, py::arg("inv_m"), py::arg("batch_size"),
+          py::arg("loss_id"), py::arg("lr_scale"), py::arg("momentum"),
+          py::arg("intercept_row"), py::arg("col_l1"), py::arg("cpos"),
+          py::arg("cneg"), py::arg("group_k") = 0);
     m.def("sgd_solve_l1", &sgd_solve_l1,
-          "all epochs with the L1 update (hipGraph replay)");
+          "all epochs with the L1 update (hipGraph replay)",
+          STEP_TENSORS, py::arg("inv_m"), py::arg("batch_size"),
+          py::arg("loss_id"), py::arg("momentum"), py::arg("intercept_row"),
+          py::arg("epochs"), py::arg("col_l1"), py::arg("cpos"),
+          py::arg("cneg"), py::arg("group_k") = 0);
     m.def("sgd_solve", &sgd_solve,
-          "all epochs of the dense solver (hipGraph-replayed)");
+          "all epochs of the dense solver (hipGraph-replayed)",
+          STEP_TENSORS, py::arg("inv_m"), py::arg("batch_size"),
+          py::arg("loss_id"), py::arg("momentum"), py::arg("intercept_row"),
+          py::arg("epochs"), py::arg("group_k") = 0);
+    #undef STEP_TENSORS
     m.def("sp_sgd_solve", &sp_sgd_solve,
           "all epochs of the sparse solver (hipGraph-replayed)");
     m.def("sp_sgd_epoch_l1", &sp_sgd_epoch_l1,

@@ -61,6 +61,7 @@ static __device__ __forceinline__ __bf16 f32_to_bf16(float x) {
 #define LOSS_LOG 0
 #define LOSS_HINGE 1
 #define LOSS_SQUARED 2
+#define LOSS_SOFTMAX 3  // k_fwd_gt_softmax only: dloss() does not know it
 
 static __device__ __forceinline__ float
 dloss(int loss_id, float z, float t) {

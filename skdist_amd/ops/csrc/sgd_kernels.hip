@@ -5,6 +5,7 @@
 // reference inventory: SURVEY.md §2.4 row 1).
 //
 //   K1 k_fwd_gt:        GT[c][i] = mask*dloss( (Xs·W)[i][c], target )
+//      k_fwd_gt_softmax (multinomial): GT = mask*(softmax over a group - t)
 //   K2 k_grad_partial:  partial[z] = Xᵀ·G  (split-K, deterministic slabs)
 //   K3 k_reduce_update: W -= lr * (Σz partial / m + λ∘W); refresh WbfT
 //
@@ -247,6 +248,193 @@ extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt(
         __bf16* dst = GT + (long long)(bn + col) * gt_stride + bm + ch;
         *(int4v*)dst = v0;
         *(int4v*)(dst + 8) = v1;
+    }
+}
+
+// ---------------------------------------------------------------------- //
+// K1, multinomial: forward GEMM + softmax cross-entropy gradient
+// grid: (m_pad/BM, ncols_pad/BN), block 256 -- k_fwd_gt's grid, GEMM tile,
+// GT layout and transposed store; `gk` stands where k_fwd_gt has loss_id.
+//
+// The gk columns of one model form a group.  A group never straddles a
+// 128-column tile: a tile holds gpt = 128 / gk groups in its first
+// gpt * gk columns (model j, class c at column
+// (j / gpt) * 128 + (j % gpt) * gk + c; ops.hip_sgd_solve lays the columns
+// out), the rest of the tile is dead.  Per row i and live group:
+//     p_c = exp(z_c - max_c z) / sum_c exp(z_c - max_c z)
+//     g_c = (p_c - [y_i == col_class[c]]) * row_w[i]
+// and g = 0 where the element does not train: row >= m, row >= n, or the
+// row's fold is the group's fold (col_fold of the group's first column).
+// A group whose first column has col_class < 0 (pad columns) is dead too;
+// dead columns enter no max or sum and store 0.
+//
+// First-cut epilogue: z goes through LDS as fp32, 64 rows at a time (the
+// [64][129] fp32 image aliases the GEMM buffers), and one lane owns one
+// (row, group): it walks the group's gk columns three times (max; exp and
+// sum, leaving e in place; divide, subtract, scale), in ascending column
+// order, so the result is deterministic and there are no atomics.  Lanes
+// of a wave hold consecutive rows, stride 129 words: conflict-free.  A
+// wave takes groups w, w + 4, ...: with gk > 32 some waves idle, and a
+// 128-wide group is one wave's work.  The tile is then read back
+// column-wise, rounded to bf16 and stored as k_fwd_gt stores it.
+//
+// __launch_bounds__(256, 4): 115 VGPRs, no AGPRs, no scratch, 36096 B of
+// LDS: 4 workgroups per CU (4 waves per SIMD), as k_fwd_gt.
+// ---------------------------------------------------------------------- //
+#define SMX_ZLD 129                    // fp32 row stride of the z image
+#define SMX_ZBYTES (64 * SMX_ZLD * 4)  // 33024, covers the 32 KiB of bufs
+#define SMX_LDS (SMX_ZBYTES + 6 * 512)
+
+extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt_softmax(
+    const __bf16* __restrict__ Xs,    // [n_pad][fa]
+    const __bf16* __restrict__ WbfT,  // [ncols_pad][fa]
+    __bf16* __restrict__ GT,          // [ncols_pad][gt_stride]
+    const float* __restrict__ y,      // [n]
+    const int* __restrict__ fold,     // [n]
+    const int* __restrict__ col_class,
+    const int* __restrict__ col_fold,
+    const int* __restrict__ col_class2,  // unused: groups have no partner
+    const float* __restrict__ row_w,     // per-row sample weights or null
+    int start, int m, long long n, int fa, int ncols_pad, int gt_stride,
+    int gk)
+{
+    extern __shared__ __attribute__((aligned(16))) char sm[];
+    float* zS = (float*)sm;                 // [64][SMX_ZLD], aliases the bufs
+    char* meta = sm + SMX_ZBYTES;
+    float* y_s = (float*)meta;              // [BM]
+    int* fold_s = (int*)(meta + 512);       // [BM]
+    int* cls_s = (int*)(meta + 1024);       // [BN]
+    int* cfold_s = (int*)(meta + 1536);     // [BN]
+    float* rw_s = (float*)(meta + 2048);    // [BM]
+    int* ok_s = (int*)(meta + 2560);        // [BM] row may train
+
+    const int tid = threadIdx.x;
+    const int bm = blockIdx.x * BM;
+    const int bn = blockIdx.y * BN;
+    const int lane = tid & 63;
+    const int w = tid >> 6;
+
+    if (tid < BM) {
+        const long long r = (long long)start + bm + tid;
+        const bool ok = r < n;
+        y_s[tid] = ok ? y[r] : 0.f;
+        fold_s[tid] = ok ? fold[r] : -9;
+        rw_s[tid] = (row_w != nullptr && ok) ? row_w[r] : 1.f;
+        ok_s[tid] = (ok && bm + tid < m) ? 1 : 0;
+    } else {
+        const int c = tid - BM;
+        cls_s[c] = col_class[bn + c];
+        cfold_s[c] = col_fold[bn + c];
+    }
+
+    const __bf16* Abase = Xs + (long long)(start + bm) * fa;
+    const __bf16* Bbase = WbfT + (long long)bn * fa;
+
+    const int wr = ((w >> 1) & 1) * 64;
+    const int wc = (w & 1) * 64;
+    const int fr = lane & 15;
+    const int fk = (lane >> 4) * 8;
+
+    // the GEMM main loop of k_fwd_gt
+    f32x4 acc[4][4] = {};
+    const int nk = fa / BK;
+    int cur = 0;
+    STAGE_TILE(bufA(0), Abase + (long long)row * fa);
+    STAGE_TILE(bufB(0), Bbase + (long long)row * fa);
+    for (int kt = 0; kt < nk; ++kt) {
+        __syncthreads();  // staged tile (glds) complete for buf[cur]
+        if (kt + 1 < nk) {
+            STAGE_TILE(bufA(cur ^ 1),
+                       Abase + (long long)row * fa + (kt + 1) * BK);
+            STAGE_TILE(bufB(cur ^ 1),
+                       Bbase + (long long)row * fa + (kt + 1) * BK);
+        }
+        bf16x8 af[4], bfr[4];
+        #pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+            af[mi] = frag_load(bufA(cur), wr + mi * 16 + fr, fk);
+        #pragma unroll
+        for (int ni = 0; ni < 4; ++ni)
+            bfr[ni] = frag_load(bufB(cur), wc + ni * 16 + fr, fk);
+        #pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+            #pragma unroll
+            for (int ni = 0; ni < 4; ++ni)
+                acc[mi][ni] =
+                    MFMA_BF16_16x16x32(af[mi], bfr[ni], acc[mi][ni]);
+        cur ^= 1;
+    }
+
+    // every wave is done reading the GEMM buffers, and the prologue's
+    // metadata is visible
+    __syncthreads();
+    const int rw = lane >> 4;
+    const int gpt = BN / gk;
+    const int ncl = gpt * gk;   // live columns of the tile
+    for (int h = 0; h < 2; ++h) {
+        if (wr == h * 64) {     // the two waves holding rows 64h .. 64h+63
+            #pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+                #pragma unroll
+                for (int ni = 0; ni < 4; ++ni)
+                    #pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        zS[(mi * 16 + rw * 4 + r) * SMX_ZLD + wc + ni * 16 +
+                           fr] = acc[mi][ni][r];
+        }
+        __syncthreads();
+        {
+            const int R = h * 64 + lane;  // this lane's row of the tile
+            const float yv = y_s[R];
+            const float rwv = rw_s[R];
+            const int fo = fold_s[R];
+            const bool rok = ok_s[R] != 0;
+            float* zrow = zS + lane * SMX_ZLD;
+            for (int g = w; g < gpt; g += 4) {
+                float* zr = zrow + g * gk;
+                const int* cl = cls_s + g * gk;
+                const bool train =
+                    rok && cl[0] >= 0 && fo != cfold_s[g * gk];
+                if (!train) {
+                    for (int c = 0; c < gk; ++c) zr[c] = 0.f;
+                    continue;
+                }
+                float mx = zr[0];
+                for (int c = 1; c < gk; ++c) mx = fmaxf(mx, zr[c]);
+                float s = 0.f;
+                for (int c = 0; c < gk; ++c) {
+                    const float e = __expf(zr[c] - mx);
+                    zr[c] = e;
+                    s += e;
+                }
+                for (int c = 0; c < gk; ++c) {
+                    const float t = (yv == (float)cl[c]) ? 1.f : 0.f;
+                    zr[c] = (zr[c] / s - t) * rwv;
+                }
+            }
+            for (int c = ncl + w; c < BN; c += 4) zrow[c] = 0.f;
+        }
+        __syncthreads();
+        #pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const int p = tid + 256 * i;
+            const int col = p >> 2;
+            const int ch = (p & 3) * 16;
+            int4v v[2];
+            #pragma unroll
+            for (int k = 0; k < 8; ++k) {
+                const unsigned lo = (unsigned short)__builtin_bit_cast(
+                    short, f32_to_bf16(zS[(ch + 2 * k) * SMX_ZLD + col]));
+                const unsigned hi = (unsigned short)__builtin_bit_cast(
+                    short, f32_to_bf16(zS[(ch + 2 * k + 1) * SMX_ZLD + col]));
+                v[k >> 2][k & 3] = (int)(lo | (hi << 16));
+            }
+            __bf16* dst =
+                GT + (long long)(bn + col) * gt_stride + bm + h * 64 + ch;
+            *(int4v*)dst = v[0];
+            *(int4v*)(dst + 8) = v[1];
+        }
+        if (h == 0) __syncthreads();  // zS is rewritten for rows 64..127
     }
 }
 
@@ -743,7 +931,9 @@ extern "C" __global__ __launch_bounds__(128) void k_reduce_update_l1(
 // ---------------------------------------------------------------------- //
 // host launcher.  col_l1 == null is the L2-only step (k_reduce_update);
 // otherwise cpos/cneg are the [fa][ncols_pad] L1 credit tables and K3 is
-// k_reduce_update_l1.  K1 and K2 are shared.
+// k_reduce_update_l1.  K1 and K2 are shared.  loss_id == LOSS_SOFTMAX
+// launches k_fwd_gt_softmax with group width group_k (2..128) as K1; every
+// other loss launches k_fwd_gt and takes group_k == 0.
 // ---------------------------------------------------------------------- //
 static hipError_t sgd_step_impl(
     const void* Xs, const void* XsT, const void* WbfT_in,
@@ -756,20 +946,33 @@ static hipError_t sgd_step_impl(
     long long fa_store, int fa, int ncols_pad,
     int gt_stride, int splitk, int loss_id,
     float lr_scale, float momentum, int intercept_row,
-    const void* col_l1, void* cpos, void* cneg,
+    const void* col_l1, void* cpos, void* cneg, int group_k,
     hipStream_t stream)
 {
     const int m_pad = (int)((m + BM - 1) / BM) * BM;
     {
         dim3 grid(m_pad / BM, ncols_pad / BN);
         size_t lds = (size_t)BN * LDC * 2 + 3600;
-        hipLaunchKernelGGL(k_fwd_gt, grid, dim3(256), lds, stream,
-                           (const __bf16*)Xs, (const __bf16*)WbfT_in,
-                           (__bf16*)GT, (const float*)y, (const int*)fold,
-                           (const int*)col_class, (const int*)col_fold,
-                           (const int*)col_class2, (const float*)row_w,
-                           (int)start, (int)m, n, fa, ncols_pad, gt_stride,
-                           loss_id);
+        if (loss_id == LOSS_SOFTMAX) {
+            if (group_k < 2 || group_k > BN) return hipErrorInvalidValue;
+            hipLaunchKernelGGL(k_fwd_gt_softmax, grid, dim3(256), SMX_LDS,
+                               stream,
+                               (const __bf16*)Xs, (const __bf16*)WbfT_in,
+                               (__bf16*)GT, (const float*)y,
+                               (const int*)fold, (const int*)col_class,
+                               (const int*)col_fold, (const int*)col_class2,
+                               (const float*)row_w, (int)start, (int)m, n,
+                               fa, ncols_pad, gt_stride, group_k);
+        } else {
+            if (group_k != 0) return hipErrorInvalidValue;
+            hipLaunchKernelGGL(k_fwd_gt, grid, dim3(256), lds, stream,
+                               (const __bf16*)Xs, (const __bf16*)WbfT_in,
+                               (__bf16*)GT, (const float*)y,
+                               (const int*)fold, (const int*)col_class,
+                               (const int*)col_fold, (const int*)col_class2,
+                               (const float*)row_w, (int)start, (int)m, n,
+                               fa, ncols_pad, gt_stride, loss_id);
+        }
         HIP_CHECK(hipGetLastError());
     }
     HIP_CHECK(launch_grad_partial(XsT, GT, partial, (int)start, m_pad, n_pad,
@@ -812,7 +1015,7 @@ extern "C" hipError_t skdist_sgd_step(
     long long start, long long m, long long n, long long n_pad,
     long long fa_store, int fa, int ncols_pad,
     int gt_stride, int splitk, int loss_id,
-    float lr_scale, float momentum, int intercept_row,
+    float lr_scale, float momentum, int intercept_row, int group_k,
     hipStream_t stream)
 {
     return sgd_step_impl(Xs, XsT, WbfT_in, GT, W, V, WbfT, partial, y,
@@ -820,7 +1023,7 @@ extern "C" hipError_t skdist_sgd_step(
                          col_l2, fmask, row_w, inv_m, start, m, n, n_pad,
                          fa_store, fa, ncols_pad, gt_stride, splitk,
                          loss_id, lr_scale, momentum, intercept_row,
-                         nullptr, nullptr, nullptr, stream);
+                         nullptr, nullptr, nullptr, group_k, stream);
 }
 
 extern "C" hipError_t skdist_sgd_step_l1(
@@ -834,7 +1037,7 @@ extern "C" hipError_t skdist_sgd_step_l1(
     long long fa_store, int fa, int ncols_pad,
     int gt_stride, int splitk, int loss_id,
     float lr_scale, float momentum, int intercept_row,
-    const void* col_l1, void* cpos, void* cneg,
+    const void* col_l1, void* cpos, void* cneg, int group_k,
     hipStream_t stream)
 {
     if (col_l1 == nullptr || cpos == nullptr || cneg == nullptr)
@@ -844,7 +1047,7 @@ extern "C" hipError_t skdist_sgd_step_l1(
                          col_l2, fmask, row_w, inv_m, start, m, n, n_pad,
                          fa_store, fa, ncols_pad, gt_stride, splitk,
                          loss_id, lr_scale, momentum, intercept_row,
-                         col_l1, cpos, cneg, stream);
+                         col_l1, cpos, cneg, group_k, stream);
 }
 
 // ---------------------------------------------------------------------- //

@@ -142,25 +142,50 @@ class DistOneVsRestClassifier(ClassifierMixin, BaseEstimator):
             self.mlb_ = MultiLabelBinarizer()
             y = self.mlb_.fit_transform(y)
 
+        y_sparse = sp.issparse(y)
+        y_ndim = 2 if y_sparse else np.asarray(y).ndim
         batched = (
             sc is not None
             and hasattr(self.estimator, "batched_multiclass_fit")
-            and self.max_negatives is None
             and not fit_params
-            and not sp.issparse(y)
-            and np.asarray(y).ndim == 1
+            and y_ndim in (1, 2)
         )
         if batched:
             from ..models.linear import FallbackToGeneric
 
+            # 1-D y without max_negatives: class targets, as before.  A
+            # label matrix (dense, sparse, or from mlb_) and any
+            # max_negatives: per-element targets and train masks, every
+            # label still a column of the one batched solve.
+            multilabel = y_ndim == 2
             try:
-                classes, ests = self.estimator.batched_multiclass_fit(
-                    X, y, cluster=sc, mode="ovr"
-                )
-                self.classes_ = classes
+                if multilabel or self.max_negatives is not None:
+                    classes, ests = self.estimator.batched_multiclass_fit(
+                        X, y, cluster=sc,
+                        mode="multilabel" if multilabel else "ovr",
+                        max_negatives=self.max_negatives,
+                        method=self.method,
+                        random_state=self.random_state,
+                    )
+                else:
+                    classes, ests = self.estimator.batched_multiclass_fit(
+                        X, y, cluster=sc, mode="ovr"
+                    )
                 self.estimators_ = ests
-                self.multilabel_ = False
-                self.label_binarizer_ = None
+                self.multilabel_ = multilabel
+                if multilabel:
+                    # the host-side state of the generic path.  For an
+                    # indicator that state (classes_ = arange(L), y_type_,
+                    # sparse_input_) does not depend on the rows, so two
+                    # rows fit it: fitting all of y sorts n * L values
+                    head = y.tocsr()[:2] if y_sparse else np.asarray(y)[:2]
+                    self.label_binarizer_ = LabelBinarizer(
+                        sparse_output=True).fit(
+                            head if head.shape[1] >= 2 else y)
+                    self.classes_ = self.label_binarizer_.classes_
+                else:
+                    self.classes_ = classes
+                    self.label_binarizer_ = None
                 _strip_sc(self)
                 return self
             except FallbackToGeneric:
@@ -230,10 +255,12 @@ class DistOneVsRestClassifier(ClassifierMixin, BaseEstimator):
         from .validation import _require_fitted
 
         _require_fitted(self, "estimators_")
-        if self.mlb_ is None and not getattr(self, "multilabel_", False):
-            out = self._try_device("predict", X)
-            if out is not None:
-                return out
+        out = self._try_device("predict", X)
+        if out is not None:
+            # multilabel: the int indicator; tag sets are rebuilt on the host
+            if self.mlb_ is not None:
+                return self.mlb_.inverse_transform(out)
+            return out
         scores = self._scores(X)
         if self.mlb_ is not None or getattr(self, "multilabel_", False):
             # _scores mixes probability columns (threshold 0.5) and raw
@@ -290,9 +317,21 @@ class DistOneVsRestClassifier(ClassifierMixin, BaseEstimator):
     # replacement for the reference's O(n·k) Python assembly loop
     # (multiclass.py:350-362; SURVEY.md §2.4 "OvR proba assembly" row)
     # ------------------------------------------------------------------ #
-    def _stacked_linear(self):
+    def _stacked_linear(self, constants=False):
+        """(coef [k, f], intercept [k], all have predict_proba), or None
+        when an estimator is not linear.  ``constants``: a
+        ``_ConstantPredictor`` (a degenerate label of a multilabel fit)
+        counts as the linear model 0.x +- 30, which lies on its side of
+        either threshold (0 on the raw score, 0.5 on the sigmoid)."""
         coefs, inters, prob = [], [], True
+        width = next((np.asarray(e.coef_).shape[-1]
+                      for e in self.estimators_ if hasattr(e, "coef_")), None)
         for est in self.estimators_:
+            if (constants and width is not None
+                    and isinstance(est, _ConstantPredictor)):
+                coefs.append(np.zeros(width, dtype=np.float32))
+                inters.append(30.0 if np.ravel(est.y_)[0] == 1 else -30.0)
+                continue
             c = getattr(est, "coef_", None)
             b = getattr(est, "intercept_", None)
             if c is None or b is None:
@@ -306,7 +345,10 @@ class DistOneVsRestClassifier(ClassifierMixin, BaseEstimator):
     def _device_predict_fn(self, method, device):
         if method not in ("predict", "predict_proba"):
             return None
-        stacked = self._stacked_linear()
+        multilabel = (
+            self.mlb_ is not None or getattr(self, "multilabel_", False))
+        stacked = self._stacked_linear(
+            constants=multilabel and method == "predict")
         if stacked is None:
             return None
         W, b, has_proba = stacked
@@ -371,6 +413,11 @@ class DistOneVsRestClassifier(ClassifierMixin, BaseEstimator):
                     Z = xb @ Wt + bt
                 if has_proba:
                     Z = torch.sigmoid(Z)
+                if method == "predict" and multilabel:
+                    # 0.5 on the sigmoid, else 0 on the raw score
+                    thr = 0.5 if has_proba else 0.0
+                    outs.append((Z > thr).to(torch.int64).cpu().numpy())
+                    continue
                 if method == "predict":
                     outs.append(Z.argmax(dim=1).cpu().numpy())
                     continue
@@ -380,14 +427,12 @@ class DistOneVsRestClassifier(ClassifierMixin, BaseEstimator):
                     Z = Z / Z.norm(dim=1, keepdim=True).clamp_min(1e-30)
                 outs.append(Z.cpu().numpy())
             out = np.concatenate(outs, axis=0)
+            if method == "predict" and multilabel:
+                return out.astype(int)
             if method == "predict":
                 return self.classes_[out]
             return out
 
-        if method == "predict" and (
-            self.mlb_ is not None or getattr(self, "multilabel_", False)
-        ):
-            return None
         return fn
 
 

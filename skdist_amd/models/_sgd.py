@@ -344,11 +344,27 @@ class ColumnSpec:
     columns of a group carry classes ``0..group_k-1`` in order, share one
     ``col_fold`` and have no one-vs-one partner.  Checked here, on the
     host, so neither solver path meets a malformed group.
+
+    ``targets`` (optional, [n, ncols] bool/uint8, original row order):
+    the target of column c on row i is ``targets[i, c]`` instead of
+    ``y[i] == col_class[c]`` -- label matrices with 0 or several positives
+    per row.  ``col_class`` / ``col_class2`` are then ignored by the target
+    and pair logic.  ``train_mask`` (optional, same shape, needs
+    ``targets``): an element trains only where it is 1, on top of the fold
+    test and the batch's row count.  Neither goes with ``group_k``.  With
+    both ``None`` every path, kernel and result is what it was without
+    them.  On the HIP path they travel as bit planes (ops.hip_sgd_solve);
+    the sparse-native solver does not take them yet.
     """
 
     def __init__(self, device, col_fold, col_class, col_lr, col_l2,
                  col_class2=None, feat_mask=None, col_l1=None,
-                 group_k=None):
+                 group_k=None, targets=None, train_mask=None):
+        if train_mask is not None and targets is None:
+            raise ValueError("train_mask needs targets")
+        if targets is not None and group_k is not None:
+            raise ValueError(
+                "targets do not go with group_k (the softmax loss)")
         if group_k is not None:
             group_k = _check_groups(group_k, col_fold, col_class,
                                     col_class2)
@@ -373,6 +389,28 @@ class ColumnSpec:
                 raise ValueError("col_l1 must be [ncols] and >= 0")
             col_l1 = as_t(l1, torch.float32) if l1.any() else None
         self.col_l1 = col_l1
+        self.targets = self._element_plane(targets, "targets", device)
+        self.train_mask = self._element_plane(train_mask, "train_mask",
+                                              device)
+
+    def _element_plane(self, a, name, device):
+        """[n, ncols] 0/1 matrix as a uint8 device tensor (None stays)."""
+        if a is None:
+            return None
+        if not isinstance(a, torch.Tensor):
+            a = np.asarray(a)
+        if a.ndim != 2 or a.shape[1] != self.ncols or a.shape[0] < 1:
+            raise ValueError(
+                f"{name} must be [n, {self.ncols}], got {tuple(a.shape)}")
+        tg = getattr(self, "targets", None)
+        if tg is not None and tuple(a.shape) != tuple(tg.shape):
+            raise ValueError(
+                f"{name} must have the shape of targets, "
+                f"{tuple(tg.shape)}, got {tuple(a.shape)}")
+        if isinstance(a, torch.Tensor):
+            return (a != 0).to(torch.uint8).to(device).contiguous()
+        return torch.as_tensor(
+            np.ascontiguousarray(a != 0).view(np.uint8), device=device)
 
 
 def _check_groups(group_k, col_fold, col_class, col_class2):
@@ -397,6 +435,15 @@ def _check_groups(group_k, col_fold, col_class, col_class2):
     if col_class2 is not None and (np.asarray(col_class2) != -1).any():
         raise ValueError("grouped columns cannot be one-vs-one columns")
     return gk
+
+
+def _check_element_rows(spec, n):
+    """targets / train_mask carry one row per row of the dataset."""
+    for name in ("targets", "train_mask"):
+        a = getattr(spec, name, None)
+        if a is not None and a.shape[0] != n:
+            raise ValueError(
+                f"ColumnSpec.{name} has {a.shape[0]} rows, the data {n}")
 
 
 def _check_loss_groups(spec, loss_id):
@@ -424,6 +471,10 @@ def batched_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
             raise ValueError(
                 "multi_class='multinomial' is not supported on the "
                 "sparse-native solver yet")
+        if getattr(spec, "targets", None) is not None:
+            raise ValueError(
+                "ColumnSpec.targets / train_mask are not supported on the "
+                "sparse-native solver yet")
         from ._sparse_sgd import sparse_sgd_fit
 
         return sparse_sgd_fit(ds, spec, loss, epochs, batch_size,
@@ -432,6 +483,7 @@ def batched_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
                               adaptive=adaptive)
     device = ds.device
     n, fa = ds.Xaug.shape
+    _check_element_rows(spec, n)
     hip = (not force_eager) and _use_hip(device)
     if hip:
         from ..ops import hip_sgd_solve
@@ -528,6 +580,9 @@ def _sgd_step_torch(Xaug, y_float, fold_id, idx, W, V, spec, loss_id,
     t = t.to(torch.float32)
     if loss_id == LOSS_SQUARED and spec.col_class[0].item() < 0:
         t = yb.unsqueeze(1).expand_as(Z)
+    targets = getattr(spec, "targets", None)
+    if targets is not None:
+        t = targets[idx].to(torch.float32)
 
     if loss_id == LOSS_SOFTMAX:
         gk = spec.group_k
@@ -549,7 +604,11 @@ def _sgd_step_torch(Xaug, y_float, fold_id, idx, W, V, spec, loss_id,
             | (yb.unsqueeze(1) == spec.col_class.unsqueeze(0).float())
             | (yb.unsqueeze(1) == c2.float())
         )
+        if targets is not None:     # no pair logic with element targets
+            pair_ok = torch.ones_like(mask)
         G = G * (mask & pair_ok).to(torch.float32)
+    if targets is not None and spec.train_mask is not None:
+        G = G * spec.train_mask[idx].to(torch.float32)
     denom = float(m)
     if row_w is not None:
         w = row_w[idx]

@@ -639,17 +639,43 @@ class _BatchedLinearBase(BaseEstimator):
 
         return out, refit_fn
 
-    def batched_multiclass_fit(self, X, y, cluster, mode="ovr"):
+    def batched_multiclass_fit(self, X, y, cluster, mode="ovr",
+                               max_negatives=None, method="ratio",
+                               random_state=None):
         """Train every one-vs-rest class (or one-vs-one pair) binary
         problem as one batched device solve; used by
         DistOneVsRest/OneVsOneClassifier.  Returns (classes, estimators)
         with estimators[i] a fitted BINARY copy of self (classes_=[0,1],
         positive class = the OvR class / the pair's second class).
+
+        ``mode="multilabel"``: ``y`` is an [n, L] 0/1 indicator (dense or
+        scipy sparse); every label is one column with per-element targets
+        (``ColumnSpec.targets``), and ``classes`` is ``arange(L)``.  A
+        label column that is all 0 or all 1 is not solved: it becomes a
+        ``_ConstantPredictor``, as on the generic path.
+
+        ``max_negatives`` (with ``method`` / ``random_state``; ``"ovr"`` and
+        ``"multilabel"``): label c trains on the rows of
+        ``_negatives_mask(Y[:, c], ...)`` -- the rows the generic path
+        trains it on -- through ``ColumnSpec.train_mask``.  A column that
+        trains n_t of the n rows gets ``(l2, l1) = _lam(n)`` and
+        ``col_lr = lr * n / n_t``.  The solver divides the summed gradient
+        by the batch size m, of which about m n_t / n rows train, so
+            step = col_lr * (sum g / m + w / (C n))
+                 ~ lr * (mean of g over the trained rows + w / (C n_t)),
+        the step of the stand-alone fit on the subset.  Columns whose mask
+        is all ones keep ``lr`` and need no mask.
         """
         if getattr(self, "class_weight", None) is not None:
             raise FallbackToGeneric(
                 "class_weight is per-binary-problem: generic path"
             )
+        if mode == "multilabel" or max_negatives is not None:
+            if mode not in ("ovr", "multilabel"):
+                raise ValueError(
+                    "max_negatives goes with mode 'ovr' or 'multilabel'")
+            return self._batched_label_fit(
+                X, y, cluster, mode, max_negatives, method, random_state)
         t0 = time.perf_counter()
         ds = _make_dataset(
             X, y,
@@ -708,6 +734,117 @@ class _BatchedLinearBase(BaseEstimator):
             ests = cluster.gather_task_results(local, len(problems))
         else:
             ests = [local[i] for i in range(len(problems))]
+        return classes, ests
+
+    def _batched_label_fit(self, X, y, cluster, mode, max_negatives,
+                           method, random_state):
+        """The per-element-target route of ``batched_multiclass_fit``: an
+        indicator matrix (``"multilabel"``), or the one-hot of a 1-D ``y``
+        with ``max_negatives`` (``"ovr"``)."""
+        import scipy.sparse as _sp
+
+        from ..distribute.multiclass import _ConstantPredictor, _negatives_mask
+
+        t0 = time.perf_counter()
+        if mode == "multilabel":
+            if _sp.issparse(y):
+                Ysp = y.tocsc()
+                if Ysp.nnz and not np.isin(Ysp.data, (0, 1)).all():
+                    raise FallbackToGeneric("targets look continuous")
+                # dense column-block-wise: never a float copy of all of Y
+                Y = np.zeros(Ysp.shape, dtype=np.uint8)
+                for lo in range(0, Ysp.shape[1], 256):
+                    Y[:, lo: lo + 256] = Ysp[:, lo: lo + 256].toarray() != 0
+            else:
+                Ya = np.asarray(y)
+                if Ya.ndim != 2 or Ya.dtype.kind not in "buif":
+                    raise FallbackToGeneric("not an indicator matrix")
+                if Ya.dtype.kind == "f":
+                    if not ((Ya == 0) | (Ya == 1)).all():
+                        raise FallbackToGeneric("targets look continuous")
+                elif Ya.dtype.kind != "b" and Ya.size and (
+                        Ya.min() < 0 or Ya.max() > 1):
+                    raise FallbackToGeneric("not an indicator matrix")
+                Y = (Ya != 0).view(np.uint8)
+            n, L = Y.shape
+            y_ds = np.zeros(n, dtype=np.int32)
+            classes = np.arange(L)
+        else:
+            y_ds = y
+        ds = _make_dataset(
+            X, y_ds, cluster=cluster, standardize=self.standardize,
+            task="cls" if mode == "multilabel" else None)
+        if getattr(ds, "is_sparse", False):
+            raise FallbackToGeneric(
+                "per-element targets are not on the sparse-native solver yet")
+        ds.set_cv_partition([])
+        if mode == "ovr":
+            classes = ds.classes_
+            if classes is None:
+                raise FallbackToGeneric("targets look continuous")
+            L = len(classes)
+            codes = ds.y_int.cpu().numpy()
+            Y = (codes[:, None] == np.arange(L)[None, :]).view(np.uint8)
+        n = ds.n
+        ids = (
+            cluster.shard_indices(L) if cluster is not None
+            else list(range(L))
+        )
+        local, solve, masks, col_lr = {}, [], [], []
+        n_pos = Y.sum(axis=0, dtype=np.int64)
+        for li in ids:
+            col = Y[:, li]
+            pos = int(n_pos[li])
+            if pos == 0 or pos == n:
+                local[li] = _ConstantPredictor().fit(None, [int(pos == n)])
+                continue
+            mask = None
+            if max_negatives is not None:
+                mask = _negatives_mask(col, max_negatives, method,
+                                       random_state)
+                if mask.all():
+                    mask = None
+            solve.append(li)
+            masks.append(mask)
+            col_lr.append(
+                self.lr if mask is None else self.lr * n / int(mask.sum()))
+        if solve:
+            l2, l1 = self._lam(n)
+            train_mask = None
+            if any(m is not None for m in masks):
+                train_mask = np.ones((n, len(solve)), dtype=np.uint8)
+                for ci, m in enumerate(masks):
+                    if m is not None:
+                        train_mask[:, ci] = m
+            spec = ColumnSpec(
+                ds.device,
+                col_fold=np.full(len(solve), -2, dtype=np.int32),
+                col_class=np.full(len(solve), 1, dtype=np.int32),
+                col_lr=np.asarray(col_lr, dtype=np.float32),
+                col_l2=np.full(len(solve), l2, dtype=np.float32),
+                col_l1=np.full(len(solve), l1, dtype=np.float32),
+                targets=(Y if len(solve) == L
+                         else np.ascontiguousarray(Y[:, solve])),
+                train_mask=train_mask,
+            )
+            W = batched_sgd_fit(
+                ds, spec, self._loss, self.epochs, self.batch_size,
+                seed=self._seed(), momentum=self.momentum,
+                lr_decay=getattr(self, "lr_decay", 0.0),
+                adaptive=getattr(self, "adaptive", None),
+            )
+            per = (time.perf_counter() - t0) / len(solve)
+            for ci, li in enumerate(solve):
+                est = sk_clone_without_sc(self)
+                est._store_fitted(ds, W[:, ci: ci + 1], True)
+                est.classes_ = np.array([0, 1])
+                est.n_features_in_ = ds.f
+                est.fit_time_ = per
+                local[li] = est
+        if cluster is not None:
+            ests = cluster.gather_task_results(local, L)
+        else:
+            ests = [local[i] for i in range(L)]
         return classes, ests
 
     # ------------------------------------------------------------------ #

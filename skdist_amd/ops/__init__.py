@@ -199,6 +199,34 @@ def softmax_columns(n_models, gk):
     return cols, ncp
 
 
+def pack_bit_plane(a, perm, n_pad, ncols_pad, chunk=1 << 15):
+    """Bit plane of a 0/1 matrix for k_fwd_gt_bits.
+
+    ``a`` [n, ncols] uint8 on the device, original row order; ``perm`` [n]
+    int64, the shuffled row order of ``Xs``.  Returns int32
+    [n_pad, ncols_pad / 32]: bit ``c & 31`` of word ``[r, c >> 5]`` is
+    ``a[perm[r], c]``; rows >= n and columns >= ncols are 0.  Packed
+    ``chunk`` rows at a time, so the int32 scratch stays at
+    ``chunk * ncols_pad * 4`` bytes.
+    """
+    n, ncols = a.shape
+    assert ncols_pad % 32 == 0 and ncols <= ncols_pad and n <= n_pad
+    dev = a.device
+    out = torch.zeros(n_pad, ncols_pad // 32, dtype=torch.int32, device=dev)
+    # bit 31 is the sign bit of an int32 word: it enters as -2^31
+    weights = torch.tensor([1 << k for k in range(31)] + [-(1 << 31)],
+                           dtype=torch.int32, device=dev)
+    for lo in range(0, n, chunk):
+        rows = a.index_select(0, perm[lo: lo + chunk])
+        blk = torch.zeros(rows.shape[0], ncols_pad, dtype=torch.int32,
+                          device=dev)
+        blk[:, :ncols] = rows != 0
+        out[lo: lo + rows.shape[0]] = (
+            blk.view(rows.shape[0], ncols_pad // 32, 32) * weights
+        ).sum(dim=2, dtype=torch.int32)
+    return out
+
+
 def hip_sgd_solve(ds, spec, loss_id, epochs, batch_size, seed, momentum,
                   lr_decay, splitk=8):
     """Full batched SGD solve on the HIP kernels (K1+K2+K3 per step).
@@ -216,6 +244,13 @@ def hip_sgd_solve(ds, spec, loss_id, epochs, batch_size, seed, momentum,
     tile layout of ``softmax_columns`` -- dead columns are pad columns --
     and gathers W back, so the caller sees compact model-major columns
     like for every other loss.
+
+    ``spec.targets`` set switches K1 to k_fwd_gt_bits through the ``*_bits``
+    entries (L2-only and L1 alike): ``spec.targets`` and, if set,
+    ``spec.train_mask`` are packed on the device into int32 bit planes,
+    columns padded to ``ncols_pad``, rows gathered by the solve's
+    permutation and zero-filled to ``n_pad``.  Each plane takes
+    ``n_pad * ncols_pad / 8`` bytes.
     """
     import numpy as np
 
@@ -280,6 +315,23 @@ def hip_sgd_solve(ds, spec, loss_id, epochs, batch_size, seed, momentum,
         rng.permutation(n), dtype=torch.int64, device=device
     )
     Xs, XsT, ys, folds, rw = ds.shuffled_views(perm)
+    targets = getattr(spec, "targets", None)
+    tbits = mbits = None
+    if targets is not None:
+        if gk is not None:
+            raise ValueError("targets do not go with the softmax loss")
+        tmask = getattr(spec, "train_mask", None)
+        for a in (targets, tmask):
+            if a is not None and tuple(a.shape) != (n, ncols):
+                raise ValueError(
+                    f"targets / train_mask must be [{n}, {ncols}], got "
+                    f"{tuple(a.shape)}")
+        tbits = pack_bit_plane(targets, perm, Xs.shape[0], ncp)
+        mbits = (
+            pack_bit_plane(tmask, perm, Xs.shape[0], ncp)
+            if tmask is not None
+            else torch.empty(0, dtype=torch.int32, device=device)
+        )
     if rw is None:
         rw_t = torch.empty(0, dtype=torch.float32, device=device)
         inv_m = torch.tensor(
@@ -293,7 +345,31 @@ def hip_sgd_solve(ds, spec, loss_id, epochs, batch_size, seed, momentum,
         inv_m = torch.tensor(
             [1.0 / max(v, 1e-30) for v in sums], dtype=torch.float32)
     col_l1 = getattr(spec, "col_l1", None)
-    if col_l1 is not None:
+    if tbits is not None:
+        l1_args = ()
+        if col_l1 is not None:
+            if not 0.0 <= momentum < 1.0:
+                raise ValueError("the L1 update needs momentum in [0, 1)")
+            l1_args = (pad_cols(col_l1, 0.0), torch.zeros_like(W),
+                       torch.zeros_like(W))
+        if lr_decay == 0.0:
+            ext.sgd_solve_bits(
+                Xs, XsT, GT, W, V, WbfT, partial, ys, folds,
+                cls_p, cfold_p, cls2_p, lr_p, l2_p, fmask, rw_t, inv_m,
+                bs, int(loss_id), float(momentum), int(ds.intercept_row),
+                int(epochs), tbits, mbits, *l1_args,
+            )
+        else:
+            for epoch in range(epochs):
+                lr_scale = 1.0 / (1.0 + lr_decay * epoch)
+                ext.sgd_epoch_bits(
+                    Xs, XsT, GT, W, V, WbfT, partial, ys, folds,
+                    cls_p, cfold_p, cls2_p, lr_p, l2_p, fmask, rw_t,
+                    inv_m, bs, int(loss_id), float(lr_scale),
+                    float(momentum), int(ds.intercept_row),
+                    tbits, mbits, *l1_args,
+                )
+    elif col_l1 is not None:
         if not 0.0 <= momentum < 1.0:
             raise ValueError("the L1 update needs momentum in [0, 1)")
         l1_p = pad_cols(col_l1, 0.0)

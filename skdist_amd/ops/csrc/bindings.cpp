@@ -35,6 +35,21 @@ extern "C" hipError_t skdist_sgd_step_l1(
     float lr_scale, float momentum, int intercept_row,
     const void* col_l1, void* cpos, void* cneg, int group_k,
     hipStream_t stream);
+// same step with per-element targets from bit planes (k_fwd_gt_bits as K1);
+// col_l1 null is the L2-only update, Mbits null means every element trains
+extern "C" hipError_t skdist_sgd_step_bits(
+    const void* Xs, const void* XsT, const void* WbfT_in,
+    void* GT, void* W, void* V, void* WbfT, void* partial,
+    const void* y, const void* fold,
+    const void* col_class, const void* col_fold, const void* col_class2,
+    const void* col_lr, const void* col_l2, const void* fmask,
+    const void* row_w, float inv_m,
+    long long start, long long m, long long n, long long n_pad,
+    long long fa_store, int fa, int ncols_pad,
+    int gt_stride, int splitk, int loss_id,
+    float lr_scale, float momentum, int intercept_row,
+    const void* col_l1, void* cpos, void* cneg,
+    const void* Tbits, const void* Mbits, hipStream_t stream);
 // K2 alone; variant: 0 the launcher's rule, 1 / 2 the 128- / 96-row tile,
 // 3 the whole-fa kernel
 extern "C" hipError_t skdist_grad_partial(
@@ -344,8 +359,42 @@ L1Args check_l1(torch::Tensor& col_l1, torch::Tensor& cpos,
     return l1;
 }
 
+// the bit planes of a solve with per-element targets: Tbits and, optionally,
+// Mbits, both int32 [n_pad, ncols_pad / 32]; tbits == nullptr is a solve
+// with class targets
+struct BitArgs {
+    const void* tbits = nullptr;
+    const void* mbits = nullptr;
+};
+
+BitArgs check_bits(const StepArgs& a, const torch::Tensor& tbits,
+                   const torch::Tensor& mbits, int64_t loss_id) {
+    TORCH_CHECK(loss_id != 3,
+                "per-element targets do not go with the softmax loss");
+    check_2d(tbits, torch::kInt32, a.n_pad, a.ncols_pad / 32, "tbits");
+    BitArgs b;
+    b.tbits = tbits.data_ptr();
+    if (mbits.numel() > 0) {
+        check_2d(mbits, torch::kInt32, a.n_pad, a.ncols_pad / 32, "mbits");
+        b.mbits = mbits.data_ptr();
+    }
+    return b;
+}
+
+// the optional L1 tensors of the *_bits entries: all three empty is the
+// L2-only update
+L1Args check_l1_opt(torch::Tensor& col_l1, torch::Tensor& cpos,
+                    torch::Tensor& cneg, torch::Tensor& W, double momentum) {
+    if (col_l1.numel() == 0 && cpos.numel() == 0 && cneg.numel() == 0)
+        return L1Args{};
+    TORCH_CHECK(col_l1.numel() > 0 && cpos.numel() > 0 && cneg.numel() > 0,
+                "col_l1, cpos and cneg (the L1 state) go together");
+    return check_l1(col_l1, cpos, cneg, W, momentum);
+}
+
 // every mini-batch step of one epoch on `st`; `l1.col_l1 == nullptr`
-// launches the L2-only step
+// launches the L2-only step, `bits.tbits != nullptr` the step with
+// per-element targets
 void enqueue_epoch(const StepArgs& a, torch::Tensor& Xs, torch::Tensor& XsT,
                    torch::Tensor& GT, torch::Tensor& W, torch::Tensor& V,
                    torch::Tensor& WbfT, torch::Tensor& partial,
@@ -357,7 +406,7 @@ void enqueue_epoch(const StepArgs& a, torch::Tensor& Xs, torch::Tensor& XsT,
                    int64_t batch_size, int64_t loss_id, float lr_scale,
                    double momentum, int64_t intercept_row,
                    const L1Args& l1, int64_t group_k, hipStream_t st,
-                   const char* who) {
+                   const char* who, const BitArgs& bits = BitArgs{}) {
     const bool has_V = V.numel() > 0;
     int64_t bi = 0;
     for (int64_t start = 0; start < a.n; start += batch_size, ++bi) {
@@ -366,7 +415,20 @@ void enqueue_epoch(const StepArgs& a, torch::Tensor& Xs, torch::Tensor& XsT,
         const void* fm = fmask.numel() ? fmask.data_ptr() : nullptr;
         const void* rw = row_w.numel() ? row_w.data_ptr() : nullptr;
         hipError_t err;
-        if (l1.col_l1 == nullptr) {
+        if (bits.tbits != nullptr) {
+            err = skdist_sgd_step_bits(
+                Xs.data_ptr(), XsT.data_ptr(), WbfT.data_ptr(),
+                GT.data_ptr(), W.data_ptr(), Vp, WbfT.data_ptr(),
+                partial.data_ptr(), y.data_ptr(), fold.data_ptr(),
+                col_class.data_ptr(), col_fold.data_ptr(),
+                col_class2.data_ptr(), col_lr.data_ptr(),
+                col_l2.data_ptr(), fm, rw, inv_p[bi],
+                start, m, a.n, a.n_pad, a.fa_store,
+                (int)a.fa, (int)a.ncols_pad, (int)a.gt_stride,
+                (int)a.splitk, (int)loss_id, lr_scale, (float)momentum,
+                (int)intercept_row, l1.col_l1, l1.cpos, l1.cneg,
+                bits.tbits, bits.mbits, st);
+        } else if (l1.col_l1 == nullptr) {
             err = skdist_sgd_step(
                 Xs.data_ptr(), XsT.data_ptr(), WbfT.data_ptr(),
                 GT.data_ptr(), W.data_ptr(), Vp, WbfT.data_ptr(),
@@ -503,6 +565,109 @@ void sgd_solve_l1(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                       fmask, row_w, inv_p, batch_size, loss_id, 1.0f,
                       momentum, intercept_row, l1, group_k, st,
                       "sgd_solve_l1");
+    };
+    run_epochs_graphed(epochs, torch_stream, body);
+}
+
+// ---- per-element targets (k_fwd_gt_bits as K1): the argument lists of
+// sgd_step / sgd_epoch / sgd_solve, then tbits and mbits (int32
+// [n_pad, ncols_pad / 32]; an empty mbits means no mask), then the optional
+// L1 tensors col_l1, cpos, cneg (all empty: the L2-only update)
+void sgd_step_bits(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
+                   torch::Tensor W, torch::Tensor V, torch::Tensor WbfT,
+                   torch::Tensor partial, torch::Tensor y,
+                   torch::Tensor fold, torch::Tensor col_class,
+                   torch::Tensor col_fold, torch::Tensor col_class2,
+                   torch::Tensor col_lr, torch::Tensor col_l2,
+                   torch::Tensor fmask, torch::Tensor row_w,
+                   int64_t start, int64_t m, int64_t loss_id,
+                   double lr_scale, double momentum, int64_t intercept_row,
+                   double inv_m, torch::Tensor tbits, torch::Tensor mbits,
+                   torch::Tensor col_l1, torch::Tensor cpos,
+                   torch::Tensor cneg) {
+    TORCH_CHECK(m >= 1, "m must be >= 1");
+    auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+                                col_class, col_fold, col_class2, col_lr,
+                                col_l2, fmask, row_w, m, momentum,
+                                intercept_row, loss_id, 0);
+    TORCH_CHECK(start >= 0 && start % 8 == 0,
+                "start must be a non-negative multiple of 8");
+    TORCH_CHECK(start + (m + 127) / 128 * 128 <= a.n_pad,
+                "start + m_pad must be <= n_pad");
+    auto bits = check_bits(a, tbits, mbits, loss_id);
+    auto l1 = check_l1_opt(col_l1, cpos, cneg, W, momentum);
+    const bool has_V = V.numel() > 0;
+    hipError_t err = skdist_sgd_step_bits(
+        Xs.data_ptr(), XsT.data_ptr(), WbfT.data_ptr(), GT.data_ptr(),
+        W.data_ptr(), has_V ? V.data_ptr() : nullptr, WbfT.data_ptr(),
+        partial.data_ptr(), y.data_ptr(), fold.data_ptr(),
+        col_class.data_ptr(), col_fold.data_ptr(), col_class2.data_ptr(),
+        col_lr.data_ptr(), col_l2.data_ptr(),
+        fmask.numel() ? fmask.data_ptr() : nullptr,
+        row_w.numel() ? row_w.data_ptr() : nullptr, (float)inv_m,
+        start, m, a.n, a.n_pad, a.fa_store, (int)a.fa,
+        (int)a.ncols_pad, (int)a.gt_stride, (int)a.splitk, (int)loss_id,
+        (float)lr_scale, (float)momentum, (int)intercept_row,
+        l1.col_l1, l1.cpos, l1.cneg, bits.tbits, bits.mbits,
+        c10::hip::getCurrentHIPStream().stream());
+    TORCH_CHECK(err == hipSuccess, "skdist_sgd_step_bits: ",
+                hipGetErrorString(err));
+}
+
+void sgd_epoch_bits(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
+                    torch::Tensor W, torch::Tensor V, torch::Tensor WbfT,
+                    torch::Tensor partial, torch::Tensor y,
+                    torch::Tensor fold, torch::Tensor col_class,
+                    torch::Tensor col_fold, torch::Tensor col_class2,
+                    torch::Tensor col_lr, torch::Tensor col_l2,
+                    torch::Tensor fmask, torch::Tensor row_w,
+                    torch::Tensor inv_m_cpu, int64_t batch_size,
+                    int64_t loss_id, double lr_scale, double momentum,
+                    int64_t intercept_row, torch::Tensor tbits,
+                    torch::Tensor mbits, torch::Tensor col_l1,
+                    torch::Tensor cpos, torch::Tensor cneg) {
+    auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+                                col_class, col_fold, col_class2, col_lr,
+                                col_l2, fmask, row_w, batch_size, momentum,
+                                intercept_row, loss_id, 0);
+    check_batches(a, batch_size, inv_m_cpu);
+    auto bits = check_bits(a, tbits, mbits, loss_id);
+    auto l1 = check_l1_opt(col_l1, cpos, cneg, W, momentum);
+    enqueue_epoch(a, Xs, XsT, GT, W, V, WbfT, partial, y, fold, col_class,
+                  col_fold, col_class2, col_lr, col_l2, fmask, row_w,
+                  (const float*)inv_m_cpu.data_ptr(), batch_size, loss_id,
+                  (float)lr_scale, momentum, intercept_row, l1, 0,
+                  c10::hip::getCurrentHIPStream().stream(),
+                  "sgd_epoch_bits", bits);
+}
+
+void sgd_solve_bits(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
+                    torch::Tensor W, torch::Tensor V, torch::Tensor WbfT,
+                    torch::Tensor partial, torch::Tensor y,
+                    torch::Tensor fold, torch::Tensor col_class,
+                    torch::Tensor col_fold, torch::Tensor col_class2,
+                    torch::Tensor col_lr, torch::Tensor col_l2,
+                    torch::Tensor fmask, torch::Tensor row_w,
+                    torch::Tensor inv_m_cpu, int64_t batch_size,
+                    int64_t loss_id, double momentum, int64_t intercept_row,
+                    int64_t epochs, torch::Tensor tbits,
+                    torch::Tensor mbits, torch::Tensor col_l1,
+                    torch::Tensor cpos, torch::Tensor cneg) {
+    auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+                                col_class, col_fold, col_class2, col_lr,
+                                col_l2, fmask, row_w, batch_size, momentum,
+                                intercept_row, loss_id, 0);
+    check_batches(a, batch_size, inv_m_cpu);
+    auto bits = check_bits(a, tbits, mbits, loss_id);
+    auto l1 = check_l1_opt(col_l1, cpos, cneg, W, momentum);
+    const float* inv_p = (const float*)inv_m_cpu.data_ptr();
+    auto torch_stream = c10::hip::getCurrentHIPStream().stream();
+    auto body = [&](hipStream_t st) {
+        enqueue_epoch(a, Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+                      col_class, col_fold, col_class2, col_lr, col_l2,
+                      fmask, row_w, inv_p, batch_size, loss_id, 1.0f,
+                      momentum, intercept_row, l1, 0, st,
+                      "sgd_solve_bits", bits);
     };
     run_epochs_graphed(epochs, torch_stream, body);
 }
@@ -1357,6 +1522,27 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           STEP_TENSORS, py::arg("inv_m"), py::arg("batch_size"),
           py::arg("loss_id"), py::arg("momentum"), py::arg("intercept_row"),
           py::arg("epochs"), py::arg("group_k") = 0);
+    #define BITS_TAIL                                                       \
+        py::arg("tbits"), py::arg("mbits"),                                 \
+        py::arg("col_l1") = torch::empty({0}),                              \
+        py::arg("cpos") = torch::empty({0}),                                \
+        py::arg("cneg") = torch::empty({0})
+    m.def("sgd_step_bits", &sgd_step_bits,
+          "fused SGD step with per-element targets (k_fwd_gt_bits)",
+          STEP_TENSORS, py::arg("start"), py::arg("m"), py::arg("loss_id"),
+          py::arg("lr_scale"), py::arg("momentum"),
+          py::arg("intercept_row"), py::arg("inv_m"), BITS_TAIL);
+    m.def("sgd_epoch_bits", &sgd_epoch_bits,
+          "one epoch of SGD steps with per-element targets",
+          STEP_TENSORS, py::arg("inv_m"), py::arg("batch_size"),
+          py::arg("loss_id"), py::arg("lr_scale"), py::arg("momentum"),
+          py::arg("intercept_row"), BITS_TAIL);
+    m.def("sgd_solve_bits", &sgd_solve_bits,
+          "all epochs with per-element targets (hipGraph replay)",
+          STEP_TENSORS, py::arg("inv_m"), py::arg("batch_size"),
+          py::arg("loss_id"), py::arg("momentum"), py::arg("intercept_row"),
+          py::arg("epochs"), BITS_TAIL);
+    #undef BITS_TAIL
     #undef STEP_TENSORS
     m.def("sp_sgd_solve", &sp_sgd_solve,
           "all epochs of the sparse solver (hipGraph-replayed)");

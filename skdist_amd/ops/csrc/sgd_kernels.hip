@@ -252,6 +252,206 @@ extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt(
 }
 
 // ---------------------------------------------------------------------- //
+// K1, per-element targets: forward GEMM + loss gradient, with the target
+// and the train mask of every (row, column) read from bit planes
+// grid: (m_pad/BM, ncols_pad/BN), block 256 -- k_fwd_gt's grid, GEMM main
+// loop, GT layout, transposed store and per-loss epilogue instantiation.
+//
+//   Tbits [n_pad][ncols_pad/32] int32: bit (c & 31) of word [r][c >> 5] is
+//         the target of kernel column c on shuffled row r
+//   Mbits same shape: the element trains only where the bit is set; a null
+//         pointer means all ones, costs no loads and selects, workgroup-
+//         uniformly, an epilogue without the mask test
+// Rows >= n and pad columns hold 0 in both planes (rows >= n are not even
+// read).  col_class / col_class2 do not exist here: the target is the bit,
+// and there is no one-vs-one test.  fold / col_fold / row_w / m keep
+// k_fwd_gt's meaning, and on a given element the arithmetic is that of
+// k_fwd_gt's general path: g = dloss(z, t) * row_w, stored as 0 where the
+// element does not train.
+//
+// A 128-column tile needs words bn/32 .. bn/32+3 of each of its 128 rows:
+// one aligned 16-byte load per row and plane (ncols_pad and bn are multiples
+// of 128), staged in the prologue word-major ([4][BM]) so that the epilogue
+// fetches one word of 4 consecutive rows with one ds_read_b128.  The 64
+// columns of a wave span two words; the bit of column colb is bit
+// (colb & 31) of word colb >> 5.
+//
+// LDS: BN*LDC*2 = 33792 (the transpose tile, aliasing the GEMM buffers)
+// + 4 * 512 (fold_s, cfold_s, rw_s, ok_s) + 2 * 2048 (the plane slabs)
+// = 39936 B <= 40960, so 4 workgroups per CU fit in 160 KiB as for k_fwd_gt
+// (y_s, cls_s, cls2_s and gen_s are gone).
+// __launch_bounds__(256, 4): 128 VGPRs, no AGPRs, no scratch (k_fwd_gt: 121).
+// ---------------------------------------------------------------------- //
+#define BITS_LDS (BN * LDC * 2 + 4 * 512 + 2 * 2048)
+
+template <int LOSS, bool HASM>
+static __device__ __forceinline__ void fwd_epilogue_bits(
+    const f32x4 (&acc)[4][4], __bf16* ldsC, const int* fold_s,
+    const int* ok_s, const float* rw_s, const int* cfold_s,
+    const int* tb_s, const int* mb_s, int wr, int wc, int fr, int rw)
+{
+    const int wq = wc >> 5;  // first of the two plane words of this wave
+    #pragma unroll
+    for (int mi = 0; mi < 4; ++mi) {
+        const int rowb = wr + mi * 16 + rw * 4;
+        const int4v fo4 = *(const int4v*)&fold_s[rowb];
+        const int4v ok4 = *(const int4v*)&ok_s[rowb];
+        const f32x4 rw4 = *(const f32x4*)&rw_s[rowb];
+        int4v tw[2], mw[2];
+        #pragma unroll
+        for (int h = 0; h < 2; ++h) {
+            tw[h] = *(const int4v*)&tb_s[(wq + h) * BM + rowb];
+            if (HASM) mw[h] = *(const int4v*)&mb_s[(wq + h) * BM + rowb];
+        }
+        #pragma unroll
+        for (int ni = 0; ni < 4; ++ni) {
+            const int colb = wc + ni * 16 + fr;
+            const int cfo = cfold_s[colb];
+            const int sh = (ni & 1) * 16 + fr;  // colb & 31
+            short4v g4;
+            #pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float z = acc[mi][ni][r];
+                bool train = (fo4[r] != cfo) && (ok4[r] != 0);
+                if (HASM)
+                    train = train &&
+                            (((unsigned)mw[ni >> 1][r] >> sh) & 1u) != 0u;
+                const float t =
+                    (((unsigned)tw[ni >> 1][r] >> sh) & 1u) ? 1.f : 0.f;
+                const float g = dloss(LOSS, z, t) * rw4[r];
+                g4[r] = __builtin_bit_cast(short,
+                                           f32_to_bf16(train ? g : 0.f));
+            }
+            *(short4v*)&ldsC[colb * LDC + rowb] = g4;
+        }
+    }
+}
+
+extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt_bits(
+    const __bf16* __restrict__ Xs,    // [n_pad][fa]
+    const __bf16* __restrict__ WbfT,  // [ncols_pad][fa]
+    __bf16* __restrict__ GT,          // [ncols_pad][gt_stride]
+    const int* __restrict__ fold,     // [n]
+    const int* __restrict__ col_fold,
+    const float* __restrict__ row_w,  // per-row sample weights or null
+    const int* __restrict__ Tbits,    // [n_pad][ncols_pad/32]
+    const int* __restrict__ Mbits,    // same, or null: every element trains
+    int start, int m, long long n, int fa, int ncols_pad, int gt_stride,
+    int loss_id)
+{
+    extern __shared__ __attribute__((aligned(16))) char sm[];
+    __bf16* ldsC = (__bf16*)sm;             // [BN][LDC], aliases the bufs
+    char* meta = sm + BN * LDC * 2;
+    int* fold_s = (int*)meta;               // [BM]
+    int* cfold_s = (int*)(meta + 512);      // [BN]
+    float* rw_s = (float*)(meta + 1024);    // [BM]
+    int* ok_s = (int*)(meta + 1536);        // [BM] row may train (< m)
+    int* tb_s = (int*)(meta + 2048);        // [4][BM] target words
+    int* mb_s = (int*)(meta + 4096);        // [4][BM] mask words
+
+    const int tid = threadIdx.x;
+    const int bm = blockIdx.x * BM;
+    const int bn = blockIdx.y * BN;
+    const int lane = tid & 63;
+    const int w = tid >> 6;
+    const int wpr = ncols_pad >> 5;         // plane words per row
+
+    if (tid < BM) {
+        const long long r = (long long)start + bm + tid;
+        const bool ok = r < n;
+        fold_s[tid] = ok ? fold[r] : -9;
+        rw_s[tid] = (row_w != nullptr && ok) ? row_w[r] : 1.f;
+        ok_s[tid] = (bm + tid < m) ? 1 : 0;
+        int4v tv = {0, 0, 0, 0};
+        if (ok) tv = *(const int4v*)(Tbits + r * wpr + (bn >> 5));
+        #pragma unroll
+        for (int k = 0; k < 4; ++k) tb_s[k * BM + tid] = tv[k];
+    } else {
+        const int c = tid - BM;
+        cfold_s[c] = col_fold[bn + c];
+        if (Mbits != nullptr) {             // workgroup-uniform
+            const long long r = (long long)start + bm + c;
+            int4v mv = {0, 0, 0, 0};
+            if (r < n) mv = *(const int4v*)(Mbits + r * wpr + (bn >> 5));
+            #pragma unroll
+            for (int k = 0; k < 4; ++k) mb_s[k * BM + c] = mv[k];
+        }
+    }
+
+    const __bf16* Abase = Xs + (long long)(start + bm) * fa;
+    const __bf16* Bbase = WbfT + (long long)bn * fa;
+
+    const int wr = ((w >> 1) & 1) * 64;
+    const int wc = (w & 1) * 64;
+    const int fr = lane & 15;
+    const int fk = (lane >> 4) * 8;
+
+    // the GEMM main loop of k_fwd_gt
+    f32x4 acc[4][4] = {};
+    const int nk = fa / BK;
+    int cur = 0;
+    STAGE_TILE(bufA(0), Abase + (long long)row * fa);
+    STAGE_TILE(bufB(0), Bbase + (long long)row * fa);
+    for (int kt = 0; kt < nk; ++kt) {
+        __syncthreads();  // staged tile (glds) complete for buf[cur]
+        if (kt + 1 < nk) {
+            STAGE_TILE(bufA(cur ^ 1),
+                       Abase + (long long)row * fa + (kt + 1) * BK);
+            STAGE_TILE(bufB(cur ^ 1),
+                       Bbase + (long long)row * fa + (kt + 1) * BK);
+        }
+        bf16x8 af[4], bfr[4];
+        #pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+            af[mi] = frag_load(bufA(cur), wr + mi * 16 + fr, fk);
+        #pragma unroll
+        for (int ni = 0; ni < 4; ++ni)
+            bfr[ni] = frag_load(bufB(cur), wc + ni * 16 + fr, fk);
+        #pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+            #pragma unroll
+            for (int ni = 0; ni < 4; ++ni)
+                acc[mi][ni] =
+                    MFMA_BF16_16x16x32(af[mi], bfr[ni], acc[mi][ni]);
+        cur ^= 1;
+    }
+
+    // epilogue, as k_fwd_gt: the barrier ends the reads of the GEMM buffers
+    // and orders the prologue's metadata writes before the reads below
+    __syncthreads();
+    const int rw = lane >> 4;
+    #define FWD_EPILOGUE_BITS(L)                                            \
+        do {                                                                \
+            if (Mbits != nullptr)                                           \
+                fwd_epilogue_bits<L, true>(acc, ldsC, fold_s, ok_s, rw_s,   \
+                                           cfold_s, tb_s, mb_s, wr, wc, fr, \
+                                           rw);                             \
+            else                                                            \
+                fwd_epilogue_bits<L, false>(acc, ldsC, fold_s, ok_s, rw_s,  \
+                                            cfold_s, tb_s, mb_s, wr, wc,    \
+                                            fr, rw);                        \
+        } while (0)
+    switch (loss_id) {
+    case LOSS_LOG: FWD_EPILOGUE_BITS(LOSS_LOG); break;
+    case LOSS_HINGE: FWD_EPILOGUE_BITS(LOSS_HINGE); break;
+    default: FWD_EPILOGUE_BITS(LOSS_SQUARED); break;
+    }
+    #undef FWD_EPILOGUE_BITS
+    __syncthreads();
+    #pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int p = tid + 256 * i;
+        const int col = p >> 3;
+        const int ch = (p & 7) * 16;
+        int4v v0 = *(int4v*)&ldsC[col * LDC + ch];
+        int4v v1 = *(int4v*)&ldsC[col * LDC + ch + 8];
+        __bf16* dst = GT + (long long)(bn + col) * gt_stride + bm + ch;
+        *(int4v*)dst = v0;
+        *(int4v*)(dst + 8) = v1;
+    }
+}
+
+// ---------------------------------------------------------------------- //
 // K1, multinomial: forward GEMM + softmax cross-entropy gradient
 // grid: (m_pad/BM, ncols_pad/BN), block 256 -- k_fwd_gt's grid, GEMM tile,
 // GT layout and transposed store; `gk` stands where k_fwd_gt has loss_id.
@@ -933,7 +1133,9 @@ extern "C" __global__ __launch_bounds__(128) void k_reduce_update_l1(
 // otherwise cpos/cneg are the [fa][ncols_pad] L1 credit tables and K3 is
 // k_reduce_update_l1.  K1 and K2 are shared.  loss_id == LOSS_SOFTMAX
 // launches k_fwd_gt_softmax with group width group_k (2..128) as K1; every
-// other loss launches k_fwd_gt and takes group_k == 0.
+// other loss launches k_fwd_gt and takes group_k == 0.  Tbits != null
+// launches k_fwd_gt_bits as K1 (not with the softmax loss), with Mbits the
+// optional mask plane; null Tbits launches the kernels above, unchanged.
 // ---------------------------------------------------------------------- //
 static hipError_t sgd_step_impl(
     const void* Xs, const void* XsT, const void* WbfT_in,
@@ -947,13 +1149,26 @@ static hipError_t sgd_step_impl(
     int gt_stride, int splitk, int loss_id,
     float lr_scale, float momentum, int intercept_row,
     const void* col_l1, void* cpos, void* cneg, int group_k,
-    hipStream_t stream)
+    const void* Tbits, const void* Mbits, hipStream_t stream)
 {
     const int m_pad = (int)((m + BM - 1) / BM) * BM;
     {
         dim3 grid(m_pad / BM, ncols_pad / BN);
         size_t lds = (size_t)BN * LDC * 2 + 3600;
-        if (loss_id == LOSS_SOFTMAX) {
+        if (Tbits != nullptr) {
+            if (loss_id == LOSS_SOFTMAX || group_k != 0)
+                return hipErrorInvalidValue;
+            hipLaunchKernelGGL(k_fwd_gt_bits, grid, dim3(256), BITS_LDS,
+                               stream,
+                               (const __bf16*)Xs, (const __bf16*)WbfT_in,
+                               (__bf16*)GT, (const int*)fold,
+                               (const int*)col_fold, (const float*)row_w,
+                               (const int*)Tbits, (const int*)Mbits,
+                               (int)start, (int)m, n, fa, ncols_pad,
+                               gt_stride, loss_id);
+        } else if (Mbits != nullptr) {
+            return hipErrorInvalidValue;  // a mask plane needs targets
+        } else if (loss_id == LOSS_SOFTMAX) {
             if (group_k < 2 || group_k > BN) return hipErrorInvalidValue;
             hipLaunchKernelGGL(k_fwd_gt_softmax, grid, dim3(256), SMX_LDS,
                                stream,
@@ -1023,7 +1238,8 @@ extern "C" hipError_t skdist_sgd_step(
                          col_l2, fmask, row_w, inv_m, start, m, n, n_pad,
                          fa_store, fa, ncols_pad, gt_stride, splitk,
                          loss_id, lr_scale, momentum, intercept_row,
-                         nullptr, nullptr, nullptr, group_k, stream);
+                         nullptr, nullptr, nullptr, group_k, nullptr,
+                         nullptr, stream);
 }
 
 extern "C" hipError_t skdist_sgd_step_l1(
@@ -1047,7 +1263,36 @@ extern "C" hipError_t skdist_sgd_step_l1(
                          col_l2, fmask, row_w, inv_m, start, m, n, n_pad,
                          fa_store, fa, ncols_pad, gt_stride, splitk,
                          loss_id, lr_scale, momentum, intercept_row,
-                         col_l1, cpos, cneg, group_k, stream);
+                         col_l1, cpos, cneg, group_k, nullptr, nullptr,
+                         stream);
+}
+
+// the step with per-element targets (k_fwd_gt_bits as K1).  col_l1 == null
+// is the L2-only update, otherwise cpos / cneg are the L1 credit tables;
+// Mbits == null trains every element the fold and row tests let through.
+extern "C" hipError_t skdist_sgd_step_bits(
+    const void* Xs, const void* XsT, const void* WbfT_in,
+    void* GT, void* W, void* V, void* WbfT, void* partial,
+    const void* y, const void* fold,
+    const void* col_class, const void* col_fold, const void* col_class2,
+    const void* col_lr, const void* col_l2, const void* fmask,
+    const void* row_w, float inv_m,
+    long long start, long long m, long long n, long long n_pad,
+    long long fa_store, int fa, int ncols_pad,
+    int gt_stride, int splitk, int loss_id,
+    float lr_scale, float momentum, int intercept_row,
+    const void* col_l1, void* cpos, void* cneg,
+    const void* Tbits, const void* Mbits, hipStream_t stream)
+{
+    if (Tbits == nullptr) return hipErrorInvalidValue;
+    if (col_l1 != nullptr && (cpos == nullptr || cneg == nullptr))
+        return hipErrorInvalidValue;
+    return sgd_step_impl(Xs, XsT, WbfT_in, GT, W, V, WbfT, partial, y,
+                         fold, col_class, col_fold, col_class2, col_lr,
+                         col_l2, fmask, row_w, inv_m, start, m, n, n_pad,
+                         fa_store, fa, ncols_pad, gt_stride, splitk,
+                         loss_id, lr_scale, momentum, intercept_row,
+                         col_l1, cpos, cneg, 0, Tbits, Mbits, stream);
 }
 
 // ---------------------------------------------------------------------- //

@@ -673,6 +673,15 @@ def batched_scores_by_fold(ds, W, model_folds, col_class, n_classes,
         and metric in hip_modes
         and (ds.classes_ is None or n_classes == 2)
     )
+    # 3..128 classes: argmax / log-sum-exp over a model's class columns in
+    # the GEMM epilogue (k_score_groups); more classes than one 128-column
+    # tile holds, and every other metric, keep the _MetricState path
+    group_modes = {"accuracy": 0, "neg_log_loss": 1}
+    use_hip_groups = (
+        _use_hip(device)
+        and metric in group_modes
+        and 3 <= n_classes <= 128
+    )
     for f in np.unique(model_folds[model_folds >= 0]):
         mids = np.flatnonzero(model_folds == f)
         cols_np = (mids[:, None] * cpm + np.arange(cpm)).ravel()
@@ -683,6 +692,10 @@ def batched_scores_by_fold(ds, W, model_folds, col_class, n_classes,
         if use_hip_kernel:
             out[mids] = _score_fold_hip(
                 ds, Wf, rows, hip_modes[metric], metric)
+            continue
+        if use_hip_groups:
+            out[mids] = _score_fold_hip_groups(
+                ds, Wf, rows, n_classes, group_modes[metric])
             continue
         spec = _Shim()
         spec.col_class = torch.as_tensor(
@@ -735,6 +748,38 @@ def _score_fold_hip(ds, Wf, rows, mode, metric):
     yd = yf[:m].to(torch.float64)
     sst = float(((yd - yd.mean()) ** 2).sum()) if m else 0.0
     return 1.0 - sse / max(sst, 1e-12)
+
+
+def _score_fold_hip_groups(ds, Wf, rows, gk, mode):
+    """One fold of a multiclass search through k_score_groups
+    (sgd_kernels.hip).  ``Wf`` [fa, n_models * gk] holds the ``gk`` class
+    columns of each model side by side; they are spread into the
+    128-column group layout of ``ops.softmax_columns``, the kernel leaves
+    hits (mode 0) or the summed negative log-likelihood (mode 1) per row
+    tile and group, and the row tiles are added here in float64.  Returns
+    accuracy or the negated mean log-loss, one value per model: z is the
+    fp32 accumulator, never rounded to bf16."""
+    from ..ops import require_hip, softmax_columns
+
+    device = ds.device
+    m = len(rows)
+    fa = ds.Xaug.shape[1]
+    nm = Wf.shape[1] // gk
+    cols, ncp = softmax_columns(nm, gk)
+    m_pad = max(128, (m + 127) // 128 * 128)
+    Xb = torch.zeros(m_pad, fa, dtype=ds.comp_dtype, device=device)
+    torch.index_select(ds.Xaug, 0, rows, out=Xb[:m])
+    yf = torch.full((m_pad,), -1e30, dtype=torch.float32, device=device)
+    yf[:m] = ds.y_float.index_select(0, rows)
+    WbfT = torch.zeros(ncp, fa, dtype=ds.comp_dtype, device=device)
+    WbfT[torch.as_tensor(cols, device=device)] = Wf.t()
+    # model j is group j: tile j // gpt, slot j % gpt; the groups past nm
+    # in the last tile are dead
+    part = torch.empty(m_pad // 128, ncp // 128 * (128 // gk),
+                       dtype=torch.float32, device=device)
+    require_hip().score_fold_groups(Xb, WbfT, yf, part, gk, mode)
+    tot = part.to(torch.float64).sum(dim=0)[:nm].cpu().numpy()
+    return (tot if mode == 0 else -tot) / max(m, 1)
 
 
 class _MetricState:

@@ -1000,6 +1000,10 @@ extern "C" hipError_t skdist_score(
     const void* Xf, const void* WbfT, const void* yf, void* out,
     long long m_pad, int fa, int ncols_pad, int mode,
     hipStream_t stream);
+extern "C" hipError_t skdist_score_groups(
+    const void* Xf, const void* WbfT, const void* yf, void* part,
+    long long m_pad, int fa, int ncols_pad, int gk, int mode,
+    hipStream_t stream);
 extern "C" hipError_t skdist_standardize(
     const void* X, const void* mean, const void* inv_std, void* out,
     long long n, int f, int fa, hipStream_t stream);
@@ -1397,6 +1401,40 @@ void score_fold(torch::Tensor Xf, torch::Tensor WbfT, torch::Tensor yf,
     TORCH_CHECK(err == hipSuccess, "score_fold: ", hipGetErrorString(err));
 }
 
+// multiclass fold scoring: WbfT in the ops.softmax_columns(n_models, gk)
+// layout, yf the encoded class index.  part [m_pad/128, (ncols_pad/128) *
+// (128/gk)]: per row tile and group, hits (mode 0) or the summed negative
+// log-likelihood (mode 1); the kernel writes every element, the caller
+// sums the row tiles
+void score_fold_groups(torch::Tensor Xf, torch::Tensor WbfT,
+                       torch::Tensor yf, torch::Tensor part, int64_t gk,
+                       int64_t mode) {
+    TORCH_CHECK(gk >= 3 && gk <= 128, "gk must be in 3..128");
+    TORCH_CHECK(mode == 0 || mode == 1, "mode must be 0 or 1");
+    check_t(Xf, torch::kBFloat16, "Xf");
+    TORCH_CHECK(Xf.dim() == 2 && Xf.size(0) % 128 == 0,
+                "m_pad must be a mult of 128");
+    const int64_t m_pad = Xf.size(0), fa = Xf.size(1);
+    TORCH_CHECK(fa >= 32 && fa % 32 == 0, "fa must be a multiple of 32");
+    check_t(WbfT, torch::kBFloat16, "WbfT");
+    TORCH_CHECK(WbfT.dim() == 2 && WbfT.size(1) == fa &&
+                WbfT.size(0) >= 128 && WbfT.size(0) % 128 == 0,
+                "WbfT must be [ncols_pad, fa], ncols_pad a mult of 128");
+    const int64_t ncols_pad = WbfT.size(0);
+    TORCH_CHECK(m_pad / 128 <= INT32_MAX && ncols_pad / 128 <= 65535,
+                "too many tiles for one launch");
+    check_vec(yf, torch::kFloat32, m_pad, "yf");
+    check_2d(part, torch::kFloat32, m_pad / 128,
+             ncols_pad / 128 * (128 / gk), "part");
+    if (m_pad == 0) return;
+    auto stream = c10::hip::getCurrentHIPStream().stream();
+    hipError_t err = skdist_score_groups(
+        Xf.data_ptr(), WbfT.data_ptr(), yf.data_ptr(), part.data_ptr(),
+        m_pad, (int)fa, (int)ncols_pad, (int)gk, (int)mode, stream);
+    TORCH_CHECK(err == hipSuccess, "score_fold_groups: ",
+                hipGetErrorString(err));
+}
+
 void standardize(torch::Tensor X, torch::Tensor mean,
                  torch::Tensor inv_std, torch::Tensor out, int64_t f) {
     check_t(out, torch::kBFloat16, "out");
@@ -1555,6 +1593,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("sp_renorm", &sp_renorm, "fold the lazy-L2 scale into W");
     m.def("score_fold", &score_fold,
           "fused fold-scoring GEMM + per-column stats");
+    m.def("score_fold_groups", &score_fold_groups,
+          "fused multiclass fold scoring: per-group hits or log-loss");
     m.def("standardize", &standardize,
           "fused standardize + augment + bf16 cast");
     m.def("hash_vectorize", &hash_vectorize,

@@ -1359,6 +1359,48 @@ extern "C" hipError_t skdist_standardize(
 // caller takes it from the fold's y in float64, _sgd._score_fold_hip)
 // grid: (m_pad/128, ncols_pad/128), block 256 (4 waves of 64x64).
 // ---------------------------------------------------------------------- //
+
+// The GEMM main loop of k_fwd_gt as an inline body for the scoring kernels:
+// acc += A[128][fa] * B[128][fa]^T, tiles double-buffered in the first
+// 32 KiB of `sm`.  On return the last fragment reads may still be in
+// flight in other waves: the caller puts a barrier before it reuses `sm`.
+static __device__ __forceinline__ void score_gemm_tile(
+    f32x4 (&acc)[4][4], char* sm, const __bf16* Abase, const __bf16* Bbase,
+    int fa, int lane, int w)
+{
+    const int wr = ((w >> 1) & 1) * 64;
+    const int wc = (w & 1) * 64;
+    const int fr = lane & 15;
+    const int fk = (lane >> 4) * 8;
+    const int nk = fa / BK;
+    int cur = 0;
+    STAGE_TILE(bufA(0), Abase + (long long)row * fa);
+    STAGE_TILE(bufB(0), Bbase + (long long)row * fa);
+    for (int kt = 0; kt < nk; ++kt) {
+        __syncthreads();  // staged tile (glds) complete for buf[cur]
+        if (kt + 1 < nk) {
+            STAGE_TILE(bufA(cur ^ 1),
+                       Abase + (long long)row * fa + (kt + 1) * BK);
+            STAGE_TILE(bufB(cur ^ 1),
+                       Bbase + (long long)row * fa + (kt + 1) * BK);
+        }
+        bf16x8 af[4], bfr[4];
+        #pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+            af[mi] = frag_load(bufA(cur), wr + mi * 16 + fr, fk);
+        #pragma unroll
+        for (int ni = 0; ni < 4; ++ni)
+            bfr[ni] = frag_load(bufB(cur), wc + ni * 16 + fr, fk);
+        #pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+            #pragma unroll
+            for (int ni = 0; ni < 4; ++ni)
+                acc[mi][ni] =
+                    MFMA_BF16_16x16x32(af[mi], bfr[ni], acc[mi][ni]);
+        cur ^= 1;
+    }
+}
+
 extern "C" __global__ __launch_bounds__(256) void k_score(
     const __bf16* __restrict__ Xf,    // [m_pad][fa] gathered fold rows
     const __bf16* __restrict__ WbfT,  // [ncols_pad][fa]
@@ -1367,8 +1409,6 @@ extern "C" __global__ __launch_bounds__(256) void k_score(
     int fa, int ncols_pad, int mode)
 {
     extern __shared__ __attribute__((aligned(16))) char sm[];
-    #define sbufA(b) ((__bf16*)(sm + (b) * 16384))
-    #define sbufB(b) ((__bf16*)(sm + 8192 + (b) * 16384))
     float* y_s = (float*)(sm + 32768);        // [128]
     float* red = (float*)(sm + 33280);        // [132] per-col partials
 
@@ -1384,58 +1424,9 @@ extern "C" __global__ __launch_bounds__(256) void k_score(
     const int wr = ((w >> 1) & 1) * 64;
     const int wc = (w & 1) * 64;
     const int fr = lane & 15;
-    const int fk = (lane >> 4) * 8;
 
     f32x4 acc[4][4] = {};
-    const int nk = fa / BK;
-    int cur = 0;
-    {   // stage first tiles (STAGE_TILE expects `row`, `lane`, `w`)
-        _Pragma("unroll") for (int i = 0; i < 2; ++i) {
-            const int c = w + 4 * i;
-            const int row = 16 * c + (lane >> 2);
-            const int slot = (lane & 3) ^ ((row >> 2) & 3);
-            __builtin_amdgcn_global_load_lds(
-                (const unsigned int*)(Abase + (long long)row * fa +
-                                      slot * 8),
-                (unsigned int*)(sbufA(0) + c * 512), 16, 0, 0);
-            __builtin_amdgcn_global_load_lds(
-                (const unsigned int*)(Bbase + (long long)row * fa +
-                                      slot * 8),
-                (unsigned int*)(sbufB(0) + c * 512), 16, 0, 0);
-        }
-    }
-    for (int kt = 0; kt < nk; ++kt) {
-        __syncthreads();
-        if (kt + 1 < nk) {
-            _Pragma("unroll") for (int i = 0; i < 2; ++i) {
-                const int c = w + 4 * i;
-                const int row = 16 * c + (lane >> 2);
-                const int slot = (lane & 3) ^ ((row >> 2) & 3);
-                __builtin_amdgcn_global_load_lds(
-                    (const unsigned int*)(Abase + (long long)row * fa +
-                                          (kt + 1) * BK + slot * 8),
-                    (unsigned int*)(sbufA(cur ^ 1) + c * 512), 16, 0, 0);
-                __builtin_amdgcn_global_load_lds(
-                    (const unsigned int*)(Bbase + (long long)row * fa +
-                                          (kt + 1) * BK + slot * 8),
-                    (unsigned int*)(sbufB(cur ^ 1) + c * 512), 16, 0, 0);
-            }
-        }
-        bf16x8 af[4], bfr[4];
-        #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-            af[mi] = frag_load(sbufA(cur), wr + mi * 16 + fr, fk);
-        #pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-            bfr[ni] = frag_load(sbufB(cur), wc + ni * 16 + fr, fk);
-        #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-            #pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-                acc[mi][ni] =
-                    MFMA_BF16_16x16x32(af[mi], bfr[ni], acc[mi][ni]);
-        cur ^= 1;
-    }
+    score_gemm_tile(acc, sm, Abase, Bbase, fa, lane, w);
     __syncthreads();
 
     // per-lane partials over this wave's 16 rows x 4 col-groups
@@ -1489,5 +1480,149 @@ extern "C" hipError_t skdist_score(
                        (const __bf16*)Xf, (const __bf16*)WbfT,
                        (const float*)yf, (float*)out, fa, ncols_pad,
                        mode);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------------- //
+// K5g: fused multiclass test-fold scoring -- k_score's GEMM tile with a
+// per-(row, group) argmax or log-sum-exp epilogue, so the decision values
+// of a 3..128-class search never reach HBM.
+// grid: (m_pad/128, ncols_pad/128), block 256.
+//
+// Xf, WbfT and yf are k_score's; yf holds the encoded class index.  The
+// columns are laid out as for k_fwd_gt_softmax (ops.softmax_columns): a
+// tile holds gpt = 128 / gk groups of gk columns, the other 128 % gk
+// columns are dead and never read.  Groups past the last model have zero
+// WbfT rows; they are scored like any other and the host drops them.
+//   mode 0 (accuracy): part[rt][g] = #rows with argmax_c z_c == y, the
+//                      lowest c winning a tie (numpy.argmax); no exp
+//   mode 1 (log-loss): part[rt][g] = sum over rows of
+//                      max_c z_c + log(sum_c exp(z_c - max_c z_c)) - z_y
+// with rt the row tile and g = blockIdx.y * gpt + the group of the tile.
+// A row with y < -1e29 (pad) adds nothing.
+//
+// Epilogue: z goes through LDS as fp32, 64 rows at a time (the [64][129]
+// image of k_fwd_gt_softmax, aliasing the GEMM buffers).  A lane owns one
+// (row, group) and walks the group's columns in ascending order; the 64
+// lanes of a wave are the 64 rows of one group, so the sum over rows is a
+// ballot + popcount (hits) or a fixed-order xor butterfly (nll): no
+// atomics, LDS or global.  Wave w takes groups w, w + 4, ... in both
+// halves and carries the total of its i-th group in lane i's `carry`
+// register; after the second half lane i stores it.  Every (row tile,
+// group) is written once with a plain store and the host adds the row
+// tiles in float64, so the result does not depend on the launch order
+// (hit counts are integers <= 128, exact in fp32).  The epilogue is
+// instantiated per mode and picked once, workgroup-uniformly.  With
+// gk > 32 some waves idle in the epilogue, as in k_fwd_gt_softmax.
+//
+// Built without packed fp32 instructions (NO_PK_F32).
+// __launch_bounds__(256, 4): 105 VGPRs, no AGPRs, no scratch, 33536 B
+// of LDS (the z image + y_s): 4 workgroups per CU, as k_fwd_gt_softmax.
+// ---------------------------------------------------------------------- //
+#define NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
+#define SCG_LDS (SMX_ZBYTES + 512)
+
+template <int MODE>
+static __device__ __forceinline__ void score_groups_epilogue(
+    const f32x4 (&acc)[4][4], float* zS, const float* y_s,
+    float* __restrict__ prow, int gk, int lane, int w)
+{
+    const int wr = ((w >> 1) & 1) * 64;
+    const int wc = (w & 1) * 64;
+    const int fr = lane & 15;
+    const int rw = lane >> 4;
+    const int gpt = BN / gk;
+    float carry = 0.f;  // lane i: total of group w + 4 * i over both halves
+    for (int h = 0; h < 2; ++h) {
+        if (wr == h * 64) {     // the two waves holding rows 64h .. 64h+63
+            #pragma unroll
+            for (int mi = 0; mi < 4; ++mi)
+                #pragma unroll
+                for (int ni = 0; ni < 4; ++ni)
+                    #pragma unroll
+                    for (int r = 0; r < 4; ++r)
+                        zS[(mi * 16 + rw * 4 + r) * SMX_ZLD + wc + ni * 16 +
+                           fr] = acc[mi][ni][r];
+        }
+        __syncthreads();
+        const float yv = y_s[h * 64 + lane];
+        const bool valid = !(yv < -1e29f);
+        // the class index, kept inside the group whatever yf holds
+        const int yi = valid ? min(max((int)yv, 0), gk - 1) : 0;
+        const float* zrow = zS + lane * SMX_ZLD;
+        for (int g = w, i = 0; g < gpt; g += 4, ++i) {
+            const float* zr = zrow + g * gk;
+            float mx = zr[0];
+            float v;
+            if (MODE == 0) {
+                int best = 0;
+                for (int c = 1; c < gk; ++c) {
+                    const float z = zr[c];
+                    if (z > mx) { mx = z; best = c; }  // ties keep the lowest
+                }
+                v = (float)__popcll(__ballot(valid && best == yi));
+            } else {
+                for (int c = 1; c < gk; ++c) mx = fmaxf(mx, zr[c]);
+                float s = 0.f;
+                for (int c = 0; c < gk; ++c) s += __expf(zr[c] - mx);
+                v = valid ? mx + __logf(s) - zr[yi] : 0.f;
+                #pragma unroll
+                for (int off = 32; off > 0; off >>= 1)
+                    v += __shfl_xor(v, off);
+            }
+            if (lane == i) carry += v;
+        }
+        if (h == 0) __syncthreads();  // zS is rewritten for rows 64..127
+    }
+    const int g = w + 4 * lane;
+    if (g < gpt) prow[g] = carry;
+}
+
+extern "C" __global__ NO_PK_F32 __launch_bounds__(256, 4)
+void k_score_groups(
+    const __bf16* __restrict__ Xf,    // [m_pad][fa] gathered fold rows
+    const __bf16* __restrict__ WbfT,  // [ncols_pad][fa], group layout
+    const float* __restrict__ yf,     // [m_pad] class index (-1e30 pad)
+    float* __restrict__ part,         // [m_pad/128][ncols_pad/128 * gpt]
+    int fa, int gk, int mode)
+{
+    extern __shared__ __attribute__((aligned(16))) char sm[];
+    float* zS = (float*)sm;                     // [64][SMX_ZLD]
+    float* y_s = (float*)(sm + SMX_ZBYTES);     // [BM]
+
+    const int tid = threadIdx.x;
+    const int bm = blockIdx.x * BM;
+    const int bn = blockIdx.y * BN;
+    const int lane = tid & 63;
+    const int w = tid >> 6;
+    if (tid < BM) y_s[tid] = yf[bm + tid];
+
+    f32x4 acc[4][4] = {};
+    score_gemm_tile(acc, sm, Xf + (long long)bm * fa,
+                    WbfT + (long long)bn * fa, fa, lane, w);
+    // every wave is done reading the GEMM buffers, and y_s is visible
+    __syncthreads();
+
+    const int gpt = BN / gk;
+    float* prow = part + ((long long)blockIdx.x * gridDim.y + blockIdx.y) * gpt;
+    if (mode == 0)
+        score_groups_epilogue<0>(acc, zS, y_s, prow, gk, lane, w);
+    else
+        score_groups_epilogue<1>(acc, zS, y_s, prow, gk, lane, w);
+}
+
+extern "C" hipError_t skdist_score_groups(
+    const void* Xf, const void* WbfT, const void* yf, void* part,
+    long long m_pad, int fa, int ncols_pad, int gk, int mode,
+    hipStream_t stream)
+{
+    if (gk < 3 || gk > BN || (mode != 0 && mode != 1) || fa < BK ||
+        fa % BK != 0 || m_pad % BM != 0 || ncols_pad % BN != 0)
+        return hipErrorInvalidValue;
+    if (m_pad == 0 || ncols_pad == 0) return hipSuccess;
+    dim3 grid((unsigned)(m_pad / BM), ncols_pad / BN);
+    hipLaunchKernelGGL(k_score_groups, grid, dim3(256), SCG_LDS, stream,
+                       (const __bf16*)Xf, (const __bf16*)WbfT,
+                       (const float*)yf, (float*)part, fa, gk, mode);
     return hipGetLastError();
 }

@@ -43,8 +43,10 @@
 // Determinism: no atomics anywhere.  K1 owns (row, column) — the dot
 // product walks the row's nnz in CSR order; K3 owns (feature, column) —
 // the gradient walks the feature's batch rows in CSC order; K2 reduces
-// fixed 1024-row chunks then one sequential pass.  Same guarantee as the
-// dense path's split-K slabs.
+// host-sized row chunks then one sequential pass.  Each pair has exactly
+// one owning lane at every legal CP because the column tile divides the
+// block (sp_tile_cols, pinned by a static_assert).  Same guarantee as
+// the dense path's split-K slabs.
 //
 // Layouts:
 //   crow   [n+1]  int64   CSR row pointers (seeded row shuffle applied)
@@ -60,12 +62,28 @@
 //     bval  [nnz_b] f32   values (CSC order)
 #include "common.h"
 
-// threads-per-column-tile: a block of 256 lanes covers ROWS_PER_BLOCK
-// work items x TC columns; TC adapts to small column counts so a 2-
-// candidate search does not idle 3/4 of each block.
-static __device__ __forceinline__ int g_tc(int cp) {
-    return cp >= 256 ? 256 : cp;  // cp is a multiple of 64
+// threads-per-column-tile: a block of 256 lanes covers 256 / TC work
+// items (rows in K1, batch-feature slots in K3 and the L1 catch-up) x TC
+// columns; TC adapts to small column counts so a 2-candidate search does
+// not idle 3/4 of each block.  A lane's item is threadIdx.x / TC and its
+// column threadIdx.x % TC, so TC must divide 256: with a TC that does
+// not (cp = 192 used as its own tile), lanes 192..255 wrap to columns
+// 0..63 of the NEXT block's item and two lanes own one (item, column).
+// A cp that does not divide 256 is therefore cut into 64-wide tiles.
+static __host__ __device__ constexpr int sp_tile_cols(int cp) {
+    // cp is a multiple of 64
+    return cp >= 256 ? 256 : (256 % cp == 0 ? cp : 64);
 }
+
+static constexpr bool sp_tile_cols_ok() {
+    for (int cp = 64; cp <= 1024; cp += 64) {
+        const int tc = sp_tile_cols(cp);
+        if (256 % tc != 0 || tc > cp) return false;
+    }
+    return true;
+}
+static_assert(sp_tile_cols_ok(),
+              "the column tile must divide the 256-lane block and fit cp");
 
 // ---------------------------------------------------------------------- //
 // K1: CSR forward + fused loss-gradient epilogue (or raw-z emit)
@@ -90,7 +108,7 @@ extern "C" __global__ __launch_bounds__(256) void k_sp_fwd(
     float* __restrict__ Z,          // [m][CP]  (emit-z mode; G null)
     long long start, long long m, int cp, int loss_id)
 {
-    const int tc = g_tc(cp);
+    const int tc = sp_tile_cols(cp);
     const int rpb = 256 / tc;
     const int c = blockIdx.y * tc + (threadIdx.x % tc);
     if (c >= cp) return;
@@ -267,7 +285,7 @@ static __device__ __forceinline__ void sp_update_body(
     const float* __restrict__ U,     // [CP] (post-K2b value)
     float* __restrict__ q, float* __restrict__ uw, float* __restrict__ ul)
 {
-    const int tc = g_tc(cp);
+    const int tc = sp_tile_cols(cp);
     const int fpb = 256 / tc;
     const int c = blockIdx.y * tc + (threadIdx.x % tc);
     if (c >= cp) return;
@@ -341,7 +359,7 @@ extern "C" __global__ __launch_bounds__(256) void k_sp_l1_catchup(
     float* __restrict__ q, float* __restrict__ uw, float* __restrict__ ul,
     long long uf, int cp)
 {
-    const int tc = g_tc(cp);
+    const int tc = sp_tile_cols(cp);
     const int fpb = 256 / tc;
     const int c = blockIdx.y * tc + (threadIdx.x % tc);
     if (c >= cp) return;
@@ -408,7 +426,7 @@ static inline void sp_fwd_launch(
     const void* col_class2, const void* rows, void* G, void* Z,
     long long start, long long m, int cp, int loss_id, hipStream_t st)
 {
-    const int tc = cp >= 256 ? 256 : cp;
+    const int tc = sp_tile_cols(cp);
     const int rpb = 256 / tc;
     long long gx = (m + rpb - 1) / rpb;
     if (gx > 2048) gx = 2048;
@@ -440,7 +458,7 @@ static hipError_t sp_sgd_step_impl(
     hipStream_t stream)
 {
     const bool l1 = col_l1 != nullptr;
-    const int tc3 = cp >= 256 ? 256 : cp;
+    const int tc3 = sp_tile_cols(cp);
     const int fpb3 = 256 / tc3;
     long long gx3 = (uf + fpb3 - 1) / fpb3;
     if (gx3 > 2048) gx3 = 2048;

@@ -221,7 +221,8 @@ def _sparse_case(seed=0, lr=0.3, l2=1e-4, n=5000, f=400, ncols=24,
         (np.flatnonzero(fold != k), np.flatnonzero(fold == k))
         for k in range(folds)])
     l1 = np.tile(np.array([0, 0, 0, 1e-4, 1e-4, 1e-4, 1e-3, 1e-3, 1e-3,
-                           1e-2, 1e-2, 1e-2], dtype=np.float32), 2)
+                           1e-2, 1e-2, 1e-2], dtype=np.float32),
+                 -(-ncols // 12))[:ncols]
     spec = ColumnSpec(
         ds.device,
         col_fold=np.tile(np.arange(folds, dtype=np.int32), ncols // folds),
@@ -233,7 +234,13 @@ def _sparse_case(seed=0, lr=0.3, l2=1e-4, n=5000, f=400, ncols=24,
 
 @pytest.mark.parametrize("adaptive", [True, False])
 def test_sparse_l1_kernels_match_eager_mirror(adaptive):
-    ds, spec, l1 = _sparse_case()
+    # 24 columns pad to 64; 150 pad to 192 (three column tiles of 64)
+    for ncols in (24, 150):
+        _check_sparse_l1_against_mirror(adaptive, ncols)
+
+
+def _check_sparse_l1_against_mirror(adaptive, ncols):
+    ds, spec, l1 = _sparse_case(ncols=ncols)
     kw = dict(epochs=5, batch_size=1024, seed=0, adaptive=adaptive)
     W_hip = sparse_sgd_fit(ds, spec, "log", **kw).cpu().numpy()
     W_eag = sparse_sgd_fit(ds, spec, "log", force_eager=True,

@@ -47,15 +47,19 @@ def _ds_and_spec(n=5000, f=400, ncols=24, seed=0, with_rw=False,
 
 
 def test_hip_solve_matches_eager_mirror():
-    ds, spec, _, _ = _ds_and_spec()
-    W_hip = sparse_sgd_fit(ds, spec, "log", epochs=5, batch_size=1024,
-                           seed=0).cpu().numpy()
-    W_eag = sparse_sgd_fit(ds, spec, "log", epochs=5, batch_size=1024,
-                           seed=0, force_eager=True).cpu().numpy()
-    # same math, different fp32 summation order
-    corr = np.corrcoef(W_hip.ravel(), W_eag.ravel())[0, 1]
-    assert corr > 0.9999, corr
-    np.testing.assert_allclose(W_hip, W_eag, atol=2e-2, rtol=0.05)
+    # 24 columns pad to 64; 150 pad to 192, the one padded width that does
+    # not divide the 256-lane block (three column tiles of 64)
+    for ncols in (24, 150):
+        ds, spec, _, _ = _ds_and_spec(ncols=ncols)
+        W_hip = sparse_sgd_fit(ds, spec, "log", epochs=5, batch_size=1024,
+                               seed=0).cpu().numpy()
+        W_eag = sparse_sgd_fit(ds, spec, "log", epochs=5, batch_size=1024,
+                               seed=0, force_eager=True).cpu().numpy()
+        assert W_hip.shape[1] == ncols
+        # same math, different fp32 summation order
+        corr = np.corrcoef(W_hip.ravel(), W_eag.ravel())[0, 1]
+        assert corr > 0.9999, (ncols, corr)
+        np.testing.assert_allclose(W_hip, W_eag, atol=2e-2, rtol=0.05)
 
 
 def test_hip_solve_with_row_weights_matches_eager():

@@ -457,12 +457,15 @@ def _check_loss_groups(spec, loss_id):
 
 def batched_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
                     momentum=0.0, lr_decay=0.0, force_eager=False,
-                    adaptive=None):
+                    adaptive=None, average=False):
     """Train all columns; returns W [f+1, ncols] fp32 on ds.device.
 
     Mini-batches walk ONE fixed seeded permutation of the rows (drawn on
     the host RNG, applied as a device gather); batch composition stays
     fixed across epochs, matching the HIP path (hip_sgd_solve).
+
+    ``average`` (False | True | int >= 1): return the mean of the
+    iterates (``_sparse_sgd.sparse_sgd_fit``); sparse-native solver only.
     """
     loss_id = _LOSS_IDS[loss] if isinstance(loss, str) else loss
     _check_loss_groups(spec, loss_id)
@@ -480,7 +483,12 @@ def batched_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
         return sparse_sgd_fit(ds, spec, loss, epochs, batch_size,
                               seed=seed, momentum=momentum,
                               lr_decay=lr_decay, force_eager=force_eager,
-                              adaptive=adaptive)
+                              adaptive=adaptive, average=average)
+    from ._sparse_sgd import _average_start
+
+    if _average_start(average) is not None:
+        raise ValueError(
+            "average= is supported on the sparse-native solver only")
     device = ds.device
     n, fa = ds.Xaug.shape
     _check_element_rows(spec, n)

@@ -265,9 +265,34 @@ class SparseDeviceDataset:
 # the solve
 # --------------------------------------------------------------------- #
 
+def _average_start(average):
+    """``average`` (False | True | int >= 1) as the row count at which
+    averaging starts, or None for no averaging."""
+    if isinstance(average, (bool, np.bool_)):
+        return 1 if average else None
+    if (isinstance(average, (int, np.integer))
+            and average >= 1):
+        return int(average)
+    raise ValueError(
+        f"average must be False, True or an int >= 1, got {average!r}")
+
+
+def _first_avg_batch(start_rows, epoch, n, batch_size):
+    """Index within ``epoch`` of the first batch after which the rows seen
+    so far (this batch included) reach ``start_rows``; n_batches when the
+    epoch ends before that."""
+    n_batches = (n + batch_size - 1) // batch_size
+    need = start_rows - epoch * n
+    if need <= 0:
+        return 0
+    if need > n:
+        return n_batches
+    return (need + batch_size - 1) // batch_size - 1
+
+
 def sparse_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
                    momentum=0.0, lr_decay=0.0, force_eager=False,
-                   adaptive=None):
+                   adaptive=None, average=False):
     """Train all columns on the sparse dataset; returns W [f+1, ncols]
     fp32 on ds.device (row f = intercept), same contract as
     ``batched_sgd_fit``.  ``momentum`` > 0 is dropped with a one-time
@@ -290,7 +315,23 @@ def sparse_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
     of f x ncols_pad (``q``) and with ``adaptive`` two more (``u``,
     ``Ulast``) — 4 GiB per table at 2^20 features x 1024 columns, on top
     of the same-sized W and Adagrad H.  L1 fits run one call per epoch
-    (no hipGraph replay); L2-only fits are untouched."""
+    (no hipGraph replay); L2-only fits are untouched.
+
+    ``average`` (False | True | int >= 1): return the mean of the
+    iterates instead of the last one (sklearn's ``SGDClassifier(average=)``
+    ): averaging starts with the first step at which the rows seen so far
+    reach the count (True = 1, every step); a count the fit never reaches
+    returns the last iterate.  The mean is kept lazily per weight (kernel
+    header, "Averaged SGD"), so a step still touches only the batch's
+    features.  Memory: allocated only in this mode, one more fp32 table
+    of f x ncols_pad (``u``) and three [ncols_pad] vectors.  Averaged fits
+    run one call per epoch (no hipGraph replay) and do not combine with
+    ``spec.col_l1`` (the L1 catch-up moves weights too)."""
+    start_rows = _average_start(average)
+    if start_rows is not None and getattr(spec, "col_l1", None) is not None:
+        raise ValueError(
+            "average= with an L1 penalty is not supported on the "
+            "sparse-native solver yet")
     if momentum > 0.0:
         warnings.warn(
             "sparse batched solve runs momentum-free SGD (a momentum "
@@ -329,6 +370,24 @@ def sparse_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
             "ul": torch.zeros_like(H) if adaptive else none,
         }
         l1["col"][:ncols] = spec.col_l1
+    avg = None
+    n_batches = (ds.n + batch_size - 1) // batch_size
+    first = [n_batches if start_rows is None
+             else _first_avg_batch(start_rows, e, ds.n, batch_size)
+             for e in range(epochs)]
+    # a count the fit never reaches is the plain fit: no table, no _avg
+    # kernels
+    if any(fb < n_batches for fb in first):
+        avg = {
+            # u rows 0..f-1 are the kernels' table; row f takes the
+            # averaged intercept when the table is returned
+            "u": torch.zeros(ds.f + 1, cp, dtype=torch.float32, device=dev),
+            "A": torch.zeros(cp, dtype=torch.float32, device=dev),
+            "Aprev": torch.zeros(cp, dtype=torch.float32, device=dev),
+            "Wbsum": torch.zeros(cp, dtype=torch.float32, device=dev),
+            "first": first,
+            "n_avg": sum(n_batches - fb for fb in first),
+        }
 
     hip = (not force_eager) and _use_hip(dev)
     if hip:
@@ -393,6 +452,30 @@ def sparse_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
                     s_host[:] = 1.0
             ext.sp_l1_flush(W[: ds.f], H, l1["U"], l1["q"], l1["u"],
                             l1["ul"])
+        elif avg is not None:
+            for epoch in range(epochs):
+                lr_scale = 1.0 / (1.0 + lr_decay * epoch)
+                ext.sp_sgd_epoch_avg(
+                    sh["crow"], sh["cidx"], sh["cval"], W[: ds.f], Wb, s,
+                    H, Hb, G, part, sh["y"], sh["fold"], rw,
+                    col["cls"], col["fold"], col["cls2"], col["lr"],
+                    col["l2"], sh["ufeat"], sh["cptr"], sh["ridx"],
+                    sh["bval"], sh["ub_ptr"], sh["inv_m"],
+                    int(batch_size), int(loss_id), float(lr_scale),
+                    avg["u"][: ds.f], avg["A"], avg["Aprev"], avg["Wbsum"],
+                    int(avg["first"][epoch]))
+                f = (np.float32(1.0)
+                     - (lr_pad * np.float32(lr_scale)) * l2_pad)
+                for _ in range(n_batches):
+                    s_host *= f
+                if float(s_host.min()) < 1e-3:
+                    # A * W is unit-free: A changes units against W
+                    ext.sp_renorm(W[: ds.f], s)
+                    avg["A"].div_(s)
+                    s.fill_(1.0)
+                    s_host[:] = 1.0
+            ext.sp_avg_finish(W[: ds.f], avg["u"][: ds.f], avg["A"],
+                              1.0 / avg["n_avg"])
         elif renorm_free:
             ext.sp_sgd_solve(
                 sh["crow"], sh["cidx"], sh["cval"], W[: ds.f], Wb, s,
@@ -421,8 +504,13 @@ def sparse_sgd_fit(ds, spec, loss, epochs, batch_size, seed=0,
                     s_host[:] = 1.0
     else:
         _sparse_sgd_eager(ds, sh, W, Wb, s, H, Hb, col, loss_id, epochs,
-                          batch_size, lr_decay, cp, l1=l1)
+                          batch_size, lr_decay, cp, l1=l1, avg=avg)
 
+    if avg is not None:
+        # the finish left the averaged true weights in u
+        out = avg["u"]
+        out[ds.f] = avg["Wbsum"] * float(np.float32(1.0 / avg["n_avg"]))
+        return out[:, :ncols]
     W[: ds.f].mul_(s.unsqueeze(0))
     W[ds.f] = Wb
     return W[:, :ncols]
@@ -484,10 +572,11 @@ def _sp_l1_touch(Wt, H, l1, rows):
 
 
 def _sparse_sgd_eager(ds, sh, W, Wb, s, H, Hb, col, loss_id, epochs,
-                      batch_size, lr_decay, cp, l1=None):
+                      batch_size, lr_decay, cp, l1=None, avg=None):
     """Eager torch mirror of the kernels' number flow (fp32 math, bf16
-    G round-trip, lazy L2 scale, lazy L1 touches).  The numerics
-    reference for the GPU tests; also the CPU execution path."""
+    G round-trip, lazy L2 scale, lazy L1 touches, lazy iterate average).
+    The numerics reference for the GPU tests; also the CPU execution
+    path."""
     dev = ds.device
     n, f = ds.n, ds.f
     crow, cidx, cval = sh["crow"], sh["cidx"], sh["cval"]
@@ -557,15 +646,26 @@ def _sparse_sgd_eager(ds, sh, W, Wb, s, H, Hb, col, loss_id, epochs,
             s.mul_(1.0 - lr * col["l2"])
             if l1 is not None:
                 l1["U"].add_(lr * l1["col"] / s)
+            avg_on = avg is not None and bi >= avg["first"][epoch]
+            if avg_on:                      # k_sp_bias_scale_avg
+                avg["Aprev"].copy_(avg["A"])
+                avg["A"].add_(s)
+                avg["Wbsum"].add_(Wb)
             GW = torch.zeros_like(Wt)
             GW.index_add_(0, jj, vv.unsqueeze(1) * G.index_select(0, rl))
             GW.mul_(im)
             if H.numel():
                 H.add_(GW * GW)
-                Wt.sub_(lr.unsqueeze(0) * GW * torch.rsqrt(H + 1e-12)
-                        / s.unsqueeze(0))
+                d = (lr.unsqueeze(0) * GW * torch.rsqrt(H + 1e-12)
+                     / s.unsqueeze(0))
             else:
-                Wt.sub_(lr.unsqueeze(0) * GW / s.unsqueeze(0))
+                d = lr.unsqueeze(0) * GW / s.unsqueeze(0)
+            Wt.sub_(d)
+            if avg is not None:
+                # k_sp_update_avg: a moved weight books Aprev * (w_old -
+                # w_new); d == 0 off the batch's features and Aprev == 0
+                # before the first averaged step
+                avg["u"][:f].add_(avg["Aprev"].unsqueeze(0) * d)
             if l1 is not None:
                 _sp_l1_touch(Wt, H, l1, uf)
         # renorm check per epoch, matching the HIP driver
@@ -576,9 +676,15 @@ def _sparse_sgd_eager(ds, sh, W, Wb, s, H, Hb, col, loss_id, epochs,
                     if l1[k].numel():
                         l1[k].mul_(s.unsqueeze(0))
                 l1["U"].mul_(s)
+            if avg is not None:
+                avg["A"].div_(s)            # A * W is unit-free
             s.fill_(1.0)
     if l1 is not None:
         _sp_l1_touch(Wt, H, l1, None)  # end-of-fit flush (k_sp_l1_flush)
+    if avg is not None and avg["n_avg"] > 0:   # k_sp_avg_finish
+        ua = avg["u"][:f]
+        ua.add_(avg["A"].unsqueeze(0) * Wt)
+        ua.mul_(float(np.float32(1.0 / avg["n_avg"])))
 
 
 # --------------------------------------------------------------------- #

@@ -700,6 +700,21 @@ extern "C" hipError_t skdist_sp_sgd_step_l1(
     float inv_m, float lr_scale,
     const void* col_l1, void* U, void* q, void* uw, void* ul,
     hipStream_t stream);
+extern "C" hipError_t skdist_sp_sgd_step_avg(
+    const void* crow, const void* cidx, const void* cval,
+    void* W, void* Wb, void* s, void* h, void* hb, void* G, void* part,
+    const void* y, const void* fold, const void* row_w,
+    const void* col_class, const void* col_fold, const void* col_class2,
+    const void* col_lr, const void* col_l2,
+    const void* ufeat, const void* cptr, const void* ridx,
+    const void* bval, long long uf,
+    long long start, long long m, int cp, int loss_id,
+    float inv_m, float lr_scale,
+    void* u, void* A, void* Aprev, void* Wbsum, int avg_on,
+    hipStream_t stream);
+extern "C" hipError_t skdist_sp_avg_finish(
+    const void* W, void* u, const void* A, long long f, int cp,
+    float inv_n, hipStream_t stream);
 extern "C" hipError_t skdist_sp_l1_flush(
     void* W, const void* h, const void* U, void* q, void* uw, void* ul,
     long long f, int cp, hipStream_t stream);
@@ -934,6 +949,114 @@ void sp_sgd_epoch_l1(torch::Tensor crow, torch::Tensor cidx,
         TORCH_CHECK(err == hipSuccess, "sp_sgd_epoch_l1: ",
                     hipGetErrorString(err));
     }
+}
+
+// averaging state of one sparse solve: u [f][CP] shaped like W, and the
+// per-column f32 vectors that go with it
+void check_sp_avg(torch::Tensor& W, torch::Tensor& u,
+                  std::initializer_list<torch::Tensor*> vecs) {
+    for (auto* t : {&W, &u}) {
+        CHECK_DEV(*t);
+        CHECK_CONT(*t);
+        TORCH_CHECK(t->scalar_type() == torch::kFloat32,
+                    "W and the averaging table u are f32");
+    }
+    TORCH_CHECK(W.dim() == 2 && u.sizes() == W.sizes(), "u must match W");
+    for (auto* t : vecs) {
+        CHECK_DEV(*t);
+        CHECK_CONT(*t);
+        TORCH_CHECK(t->scalar_type() == torch::kFloat32 && t->dim() == 1 &&
+                    t->numel() == W.size(1),
+                    "averaging vectors must be f32 [cp]");
+    }
+}
+
+// averaged twin of sp_sgd_epoch (L2-only): same positional arguments,
+// then the averaging state (zero-initialised by the caller, carried across
+// epochs) and the index within this epoch of the first averaged batch
+// (0: the whole epoch; n_batches or more: none).  One call per epoch, no
+// graph capture.
+void sp_sgd_epoch_avg(torch::Tensor crow, torch::Tensor cidx,
+                      torch::Tensor cval, torch::Tensor W, torch::Tensor Wb,
+                      torch::Tensor s, torch::Tensor h, torch::Tensor hb,
+                      torch::Tensor G, torch::Tensor part,
+                      torch::Tensor y, torch::Tensor fold,
+                      torch::Tensor row_w,
+                      torch::Tensor col_class, torch::Tensor col_fold,
+                      torch::Tensor col_class2, torch::Tensor col_lr,
+                      torch::Tensor col_l2, torch::Tensor ufeat,
+                      torch::Tensor cptr, torch::Tensor ridx,
+                      torch::Tensor bval, torch::Tensor ub_ptr_cpu,
+                      torch::Tensor inv_m_cpu, int64_t batch_size,
+                      int64_t loss_id, double lr_scale,
+                      torch::Tensor u, torch::Tensor A, torch::Tensor Aprev,
+                      torch::Tensor Wbsum, int64_t first_avg_batch) {
+    for (auto* t : {&crow, &cidx, &cval, &W, &Wb, &s, &G, &part, &y,
+                    &fold, &col_class, &col_fold, &col_class2, &col_lr,
+                    &col_l2, &ufeat, &cptr, &ridx, &bval}) {
+        CHECK_DEV(*t);
+        CHECK_CONT(*t);
+    }
+    TORCH_CHECK(!ub_ptr_cpu.is_cuda() && !inv_m_cpu.is_cuda(),
+                "ub_ptr/inv_m must be CPU tensors");
+    TORCH_CHECK(crow.scalar_type() == torch::kInt64, "crow must be i64");
+    TORCH_CHECK(cidx.scalar_type() == torch::kInt32, "cidx must be i32");
+    TORCH_CHECK(G.scalar_type() == torch::kBFloat16, "G must be bf16");
+    TORCH_CHECK(batch_size > 0 && first_avg_batch >= 0,
+                "batch_size must be positive, first_avg_batch >= 0");
+    check_sp_avg(W, u, {&Wb, &s, &A, &Aprev, &Wbsum});
+    const int64_t cp = W.size(1);
+    check_cp(cp);
+    check_adagrad(W, h);
+    TORCH_CHECK(hb.numel() == (h.numel() ? cp : 0),
+                "hb goes with the Adagrad accumulator h");
+    const int64_t n = crow.size(0) - 1;
+    TORCH_CHECK(G.size(0) >= std::min<int64_t>(batch_size, n) &&
+                G.size(1) == cp, "G buffer too small");
+    const int64_t nb = (n + batch_size - 1) / batch_size;
+    TORCH_CHECK(ub_ptr_cpu.numel() >= nb + 1 && inv_m_cpu.numel() >= nb,
+                "ub_ptr/inv_m shorter than the batch count");
+    const int64_t* ub = (const int64_t*)ub_ptr_cpu.data_ptr();
+    TORCH_CHECK(ub[nb] <= ufeat.numel() && ub[nb] + 1 <= cptr.numel(),
+                "ub_ptr runs past ufeat/cptr");
+    const float* inv_p = (const float*)inv_m_cpu.data_ptr();
+    auto stream = c10::hip::getCurrentHIPStream().stream();
+    int64_t bi = 0;
+    for (int64_t start = 0; start < n; start += batch_size, ++bi) {
+        const int64_t m = std::min(batch_size, n - start);
+        const int64_t ub0 = ub[bi], uf = ub[bi + 1] - ub[bi];
+        hipError_t err = skdist_sp_sgd_step_avg(
+            crow.data_ptr(), cidx.data_ptr(), cval.data_ptr(),
+            W.data_ptr(), Wb.data_ptr(), s.data_ptr(),
+            h.numel() ? h.data_ptr() : nullptr,
+            hb.numel() ? hb.data_ptr() : nullptr, G.data_ptr(),
+            part.data_ptr(), y.data_ptr(), fold.data_ptr(),
+            row_w.numel() ? row_w.data_ptr() : nullptr,
+            col_class.data_ptr(), col_fold.data_ptr(),
+            col_class2.data_ptr(), col_lr.data_ptr(), col_l2.data_ptr(),
+            (const int*)ufeat.data_ptr() + ub0,
+            (const long long*)cptr.data_ptr() + ub0,
+            ridx.data_ptr(), bval.data_ptr(), uf,
+            start, m, (int)cp, (int)loss_id, inv_p[bi],
+            (float)lr_scale, u.data_ptr(), A.data_ptr(), Aprev.data_ptr(),
+            Wbsum.data_ptr(), bi >= first_avg_batch ? 1 : 0, stream);
+        TORCH_CHECK(err == hipSuccess, "sp_sgd_epoch_avg: ",
+                    hipGetErrorString(err));
+    }
+}
+
+// end of an averaged fit: u <- (u + A * W) * inv_n over all
+// (feature, column); u is the returned table
+void sp_avg_finish(torch::Tensor W, torch::Tensor u, torch::Tensor A,
+                   double inv_n) {
+    check_sp_avg(W, u, {&A});
+    check_cp(W.size(1));
+    auto stream = c10::hip::getCurrentHIPStream().stream();
+    hipError_t err = skdist_sp_avg_finish(
+        W.data_ptr(), u.data_ptr(), A.data_ptr(), W.size(0),
+        (int)W.size(1), (float)inv_n, stream);
+    TORCH_CHECK(err == hipSuccess, "sp_avg_finish: ",
+                hipGetErrorString(err));
 }
 
 // end-of-fit L1 flush over all (feature, column)
@@ -1586,6 +1709,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "all epochs of the sparse solver (hipGraph-replayed)");
     m.def("sp_sgd_epoch_l1", &sp_sgd_epoch_l1,
           "one epoch of sparse SGD steps with the lazy L1 update");
+    m.def("sp_sgd_epoch_avg", &sp_sgd_epoch_avg,
+          "one epoch of sparse SGD steps with the lazy iterate average");
+    m.def("sp_avg_finish", &sp_avg_finish,
+          "end of an averaged fit: u <- (u + A * W) * inv_n");
     m.def("sp_l1_flush", &sp_l1_flush, "end-of-fit L1 flush");
     m.def("sp_renorm_l1", &sp_renorm_l1,
           "fold the lazy-L2 scale into W and the L1 tables");

@@ -40,6 +40,20 @@
 // by the accumulated credit equals the per-step clips it replaces.
 // Extra tables [f][CP] f32: Q (always), Uw and Ul (adaptive only).
 //
+// Averaged SGD (the *_avg kernels; eager twin in _sparse_sgd.py): the mean
+// of the true iterates s_t * w_t over the averaged steps t0..T, kept
+// LAZILY per weight (Xu 2011; sklearn's sparse ASGD), in stored units:
+//
+//     A_t[c]     = sum_{tau = t0..t} s_tau[c]               (K2b_avg)
+//     Acc_t[j,c] = sum_tau s_tau w_tau[j,c] = u[j,c] + A_t[c] * w_t[j,c]
+//     a weight K3 moves by d = step / s' at step t:  u += A_{t-1}[c] * d
+//     an untouched weight: nothing
+//     end of fit: avg[j,c] = (u + A_T * w) / N              (k_sp_avg_finish)
+//
+// Before t0, A == Aprev == 0 and u does not move.  The intercept is dense:
+// Wbsum[c] += Wb'[c] per averaged step.  A renorm (W *= s, s = 1) keeps
+// A * w with A /= s, done by the caller.  One extra table u [f][CP] f32.
+//
 // Determinism: no atomics anywhere.  K1 owns (row, column) — the dot
 // product walks the row's nnz in CSR order; K3 owns (feature, column) —
 // the gradient walks the feature's batch rows in CSC order; K2 reduces
@@ -84,6 +98,11 @@ static constexpr bool sp_tile_cols_ok() {
 }
 static_assert(sp_tile_cols_ok(),
               "the column tile must divide the 256-lane block and fit cp");
+
+// the averaged-SGD kernels are built without packed fp32 instructions
+// (as k_score_groups in sgd_kernels.hip); every other kernel of this file
+// is compiled as before
+#define NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
 
 // ---------------------------------------------------------------------- //
 // K1: CSR forward + fused loss-gradient epilogue (or raw-z emit)
@@ -184,13 +203,15 @@ extern "C" __global__ __launch_bounds__(256) void k_sp_colsum(
 // K2b: reduce chunks -> intercept update + lazy-scale advance
 // grid: ceil(CP/256), block 256.  With `hb` non-null the intercept step
 // is Adagrad-normalized (hb accumulates the squared mean-gradient).
-template <bool L1>
+template <bool L1, bool AVG = false>
 static __device__ __forceinline__ void sp_bias_scale_body(
     const float* __restrict__ part, float* __restrict__ Wb,
     float* __restrict__ s, float* __restrict__ hb,
     const float* __restrict__ col_lr, const float* __restrict__ col_l2,
     int n_chunks, int cp, float inv_m, float lr_scale,
-    const float* __restrict__ col_l1, float* __restrict__ U)
+    const float* __restrict__ col_l1, float* __restrict__ U,
+    float* __restrict__ A = nullptr, float* __restrict__ Aprev = nullptr,
+    float* __restrict__ Wbsum = nullptr, int avg_on = 0)
 {
     const int c = blockIdx.x * 256 + threadIdx.x;
     if (c >= cp) return;
@@ -212,10 +233,17 @@ static __device__ __forceinline__ void sp_bias_scale_body(
         hb[c] = h;
         step = lr * g * __frsqrt_rn(h + 1e-12f);
     }
-    Wb[c] -= step;                            // no L2 on the intercept
+    const float wbn = Wb[c] - step;           // no L2 on the intercept
+    Wb[c] = wbn;
     const float sn = s[c] * (1.f - lr * col_l2[c]);
     s[c] = sn;                                // lazy decay of all of W
     if (L1) U[c] += lr * col_l1[c] / sn;      // stored-unit L1 threshold
+    if (AVG && avg_on) {                      // uniform: this step averages
+        const float a = A[c];
+        Aprev[c] = a;                         // what K3 credits moved weights
+        A[c] = a + sn;
+        Wbsum[c] += wbn;
+    }
 }
 
 extern "C" __global__ __launch_bounds__(256) void k_sp_bias_scale(
@@ -237,6 +265,23 @@ extern "C" __global__ __launch_bounds__(256) void k_sp_bias_scale_l1(
 {
     sp_bias_scale_body<true>(part, Wb, s, hb, col_lr, col_l2, n_chunks,
                              cp, inv_m, lr_scale, col_l1, U);
+}
+
+// averaged-SGD twin: with `avg_on` the step also advances the per-column
+// scale sum A (keeping the pre-step value in Aprev for K3) and the dense
+// intercept sum; with it off all three stay as they are
+extern "C" __global__ NO_PK_F32 __launch_bounds__(256)
+void k_sp_bias_scale_avg(
+    const float* __restrict__ part, float* __restrict__ Wb,
+    float* __restrict__ s, float* __restrict__ hb,
+    const float* __restrict__ col_lr, const float* __restrict__ col_l2,
+    int n_chunks, int cp, float inv_m, float lr_scale,
+    float* __restrict__ A, float* __restrict__ Aprev,
+    float* __restrict__ Wbsum, int avg_on)
+{
+    sp_bias_scale_body<false, true>(part, Wb, s, hb, col_lr, col_l2,
+                                    n_chunks, cp, inv_m, lr_scale, nullptr,
+                                    nullptr, A, Aprev, Wbsum, avg_on);
 }
 
 // One touch of weight e = (j, c): bring its L1 credit up to the column's
@@ -270,7 +315,7 @@ static __device__ __forceinline__ float sp_l1_touch(
 // the lazy L2 scale path is untouched, so regularization stays exactly
 // the dense solver's per-step decay.
 // ---------------------------------------------------------------------- //
-template <bool L1>
+template <bool L1, bool AVG = false>
 static __device__ __forceinline__ void sp_update_body(
     const int* __restrict__ ufeat,   // [uf]
     const long long* __restrict__ cptr,  // [uf+1]
@@ -283,7 +328,9 @@ static __device__ __forceinline__ void sp_update_body(
     const float* __restrict__ col_lr,
     long long uf, int cp, float inv_m, float lr_scale,
     const float* __restrict__ U,     // [CP] (post-K2b value)
-    float* __restrict__ q, float* __restrict__ uw, float* __restrict__ ul)
+    float* __restrict__ q, float* __restrict__ uw, float* __restrict__ ul,
+    float* __restrict__ ua = nullptr,        // [f][CP] lazy-average table
+    const float* __restrict__ Aprev = nullptr)  // [CP] A before this step
 {
     const int tc = sp_tile_cols(cp);
     const int fpb = 256 / tc;
@@ -317,6 +364,11 @@ static __device__ __forceinline__ void sp_update_body(
     if (L1) {
         const float w = W[e] - step / s[c];
         W[e] = sp_l1_touch(w, e, U[c], h, q, uw, ul);
+    } else if (AVG) {
+        // one quotient moves W and credits u: the two cannot disagree
+        const float d = step / s[c];
+        W[e] -= d;
+        ua[e] += Aprev[c] * d;
     } else {
         W[e] -= step / s[c];
     }
@@ -348,6 +400,23 @@ extern "C" __global__ __launch_bounds__(256) void k_sp_update_l1(
 {
     sp_update_body<true>(ufeat, cptr, ridx, bval, G, W, h, s, col_lr, uf,
                          cp, inv_m, lr_scale, U, q, uw, ul);
+}
+
+// averaged-SGD twin of k_sp_update (L2-only): a moved weight also books
+// Aprev[c] * (w_old - w_new) into the lazy-average table u
+extern "C" __global__ NO_PK_F32 __launch_bounds__(256)
+void k_sp_update_avg(
+    const int* __restrict__ ufeat, const long long* __restrict__ cptr,
+    const int* __restrict__ ridx, const float* __restrict__ bval,
+    const __bf16* __restrict__ G, float* __restrict__ W,
+    float* __restrict__ h, const float* __restrict__ s,
+    const float* __restrict__ col_lr,
+    long long uf, int cp, float inv_m, float lr_scale,
+    float* __restrict__ u, const float* __restrict__ Aprev)
+{
+    sp_update_body<false, true>(ufeat, cptr, ridx, bval, G, W, h, s, col_lr,
+                                uf, cp, inv_m, lr_scale, nullptr, nullptr,
+                                nullptr, nullptr, u, Aprev);
 }
 
 // L1 catch-up: touch every (batch feature, column) BEFORE the forward, so
@@ -397,6 +466,20 @@ extern "C" __global__ __launch_bounds__(256) void k_sp_renorm(
     W[(long long)blockIdx.x * cp + c] *= s[c];
 }
 
+// end of an averaged fit: u <- (u + A[c] * W) * inv_n, the mean of the
+// true iterates (already in true units: no s).  grid: (f, CP/256),
+// block 256
+extern "C" __global__ NO_PK_F32 __launch_bounds__(256)
+void k_sp_avg_finish(
+    const float* __restrict__ W, float* __restrict__ u,
+    const float* __restrict__ A, int cp, float inv_n)
+{
+    const int c = blockIdx.y * 256 + threadIdx.x;
+    if (c >= cp) return;
+    const long long e = (long long)blockIdx.x * cp + c;
+    u[e] = (u[e] + A[c] * W[e]) * inv_n;
+}
+
 // L1 mode: the per-weight stored-unit L1 tables change units with W
 // (the per-column U is scaled by the caller).  uw / ul null = adaptive off
 extern "C" __global__ __launch_bounds__(256) void k_sp_renorm_l1(
@@ -443,7 +526,10 @@ static inline void sp_fwd_launch(
 
 // col_l1 == null: the L2-only step.  Otherwise U [CP] and q [f][CP]
 // (and uw, ul [f][CP] when h is set) carry the L1 state, the catch-up
-// runs first and K2b / K3 are their _l1 variants.
+// runs first and K2b / K3 are their _l1 variants.  u == null: no
+// averaging.  Otherwise (L2-only) A, Aprev, Wbsum [CP] and u [f][CP] carry
+// the lazy average, K2b / K3 are their _avg variants and `avg_on` says
+// whether this step is an averaged one.
 static hipError_t sp_sgd_step_impl(
     const void* crow, const void* cidx, const void* cval,
     void* W, void* Wb, void* s, void* h, void* hb, void* G, void* part,
@@ -455,9 +541,11 @@ static hipError_t sp_sgd_step_impl(
     long long start, long long m, int cp, int loss_id,
     float inv_m, float lr_scale,
     const void* col_l1, void* U, void* q, void* uw, void* ul,
+    void* u, void* A, void* Aprev, void* Wbsum, int avg_on,
     hipStream_t stream)
 {
     const bool l1 = col_l1 != nullptr;
+    const bool avg = u != nullptr;
     const int tc3 = sp_tile_cols(cp);
     const int fpb3 = 256 / tc3;
     long long gx3 = (uf + fpb3 - 1) / fpb3;
@@ -486,7 +574,15 @@ static hipError_t sp_sgd_step_impl(
     }
     {
         dim3 grid((unsigned)((cp + 255) / 256));
-        if (!l1)
+        if (avg)
+            hipLaunchKernelGGL(k_sp_bias_scale_avg, grid, dim3(256), 0,
+                               stream,
+                               (const float*)part, (float*)Wb, (float*)s,
+                               (float*)hb,
+                               (const float*)col_lr, (const float*)col_l2,
+                               nch, cp, inv_m, lr_scale, (float*)A,
+                               (float*)Aprev, (float*)Wbsum, avg_on);
+        else if (!l1)
             hipLaunchKernelGGL(k_sp_bias_scale, grid, dim3(256), 0, stream,
                                (const float*)part, (float*)Wb, (float*)s,
                                (float*)hb,
@@ -503,7 +599,15 @@ static hipError_t sp_sgd_step_impl(
         HIP_CHECK(hipGetLastError());
     }
     if (uf > 0) {
-        if (!l1)
+        if (avg)
+            hipLaunchKernelGGL(k_sp_update_avg, grid3, dim3(256), 0, stream,
+                               (const int*)ufeat, (const long long*)cptr,
+                               (const int*)ridx, (const float*)bval,
+                               (const __bf16*)G, (float*)W, (float*)h,
+                               (const float*)s, (const float*)col_lr, uf,
+                               cp, inv_m, lr_scale, (float*)u,
+                               (const float*)Aprev);
+        else if (!l1)
             hipLaunchKernelGGL(k_sp_update, grid3, dim3(256), 0, stream,
                                (const int*)ufeat, (const long long*)cptr,
                                (const int*)ridx, (const float*)bval,
@@ -539,7 +643,43 @@ extern "C" hipError_t skdist_sp_sgd_step(
                             col_lr, col_l2, ufeat, cptr, ridx, bval, uf,
                             start, m, cp, loss_id, inv_m, lr_scale,
                             nullptr, nullptr, nullptr, nullptr, nullptr,
-                            stream);
+                            nullptr, nullptr, nullptr, nullptr, 0, stream);
+}
+
+extern "C" hipError_t skdist_sp_sgd_step_avg(
+    const void* crow, const void* cidx, const void* cval,
+    void* W, void* Wb, void* s, void* h, void* hb, void* G, void* part,
+    const void* y, const void* fold, const void* row_w,
+    const void* col_class, const void* col_fold, const void* col_class2,
+    const void* col_lr, const void* col_l2,
+    const void* ufeat, const void* cptr, const void* ridx,
+    const void* bval, long long uf,
+    long long start, long long m, int cp, int loss_id,
+    float inv_m, float lr_scale,
+    void* u, void* A, void* Aprev, void* Wbsum, int avg_on,
+    hipStream_t stream)
+{
+    if (u == nullptr || A == nullptr || Aprev == nullptr ||
+        Wbsum == nullptr)
+        return hipErrorInvalidValue;
+    return sp_sgd_step_impl(crow, cidx, cval, W, Wb, s, h, hb, G, part, y,
+                            fold, row_w, col_class, col_fold, col_class2,
+                            col_lr, col_l2, ufeat, cptr, ridx, bval, uf,
+                            start, m, cp, loss_id, inv_m, lr_scale,
+                            nullptr, nullptr, nullptr, nullptr, nullptr,
+                            u, A, Aprev, Wbsum, avg_on, stream);
+}
+
+extern "C" hipError_t skdist_sp_avg_finish(
+    const void* W, void* u, const void* A, long long f, int cp,
+    float inv_n, hipStream_t stream)
+{
+    if (f == 0) return hipSuccess;
+    dim3 grid((unsigned)f, (unsigned)((cp + 255) / 256));
+    hipLaunchKernelGGL(k_sp_avg_finish, grid, dim3(256), 0, stream,
+                       (const float*)W, (float*)u, (const float*)A, cp,
+                       inv_n);
+    return hipGetLastError();
 }
 
 extern "C" hipError_t skdist_sp_sgd_step_l1(
@@ -564,7 +704,8 @@ extern "C" hipError_t skdist_sp_sgd_step_l1(
                             fold, row_w, col_class, col_fold, col_class2,
                             col_lr, col_l2, ufeat, cptr, ridx, bval, uf,
                             start, m, cp, loss_id, inv_m, lr_scale,
-                            col_l1, U, q, uw, ul, stream);
+                            col_l1, U, q, uw, ul, nullptr, nullptr,
+                            nullptr, nullptr, 0, stream);
 }
 
 extern "C" hipError_t skdist_sp_l1_flush(

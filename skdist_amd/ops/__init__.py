@@ -345,71 +345,36 @@ def hip_sgd_solve(ds, spec, loss_id, epochs, batch_size, seed, momentum,
         inv_m = torch.tensor(
             [1.0 / max(v, 1e-30) for v in sums], dtype=torch.float32)
     col_l1 = getattr(spec, "col_l1", None)
-    if tbits is not None:
-        l1_args = ()
-        if col_l1 is not None:
-            if not 0.0 <= momentum < 1.0:
-                raise ValueError("the L1 update needs momentum in [0, 1)")
-            l1_args = (pad_cols(col_l1, 0.0), torch.zeros_like(W),
-                       torch.zeros_like(W))
-        if lr_decay == 0.0:
-            ext.sgd_solve_bits(
-                Xs, XsT, GT, W, V, WbfT, partial, ys, folds,
-                cls_p, cfold_p, cls2_p, lr_p, l2_p, fmask, rw_t, inv_m,
-                bs, int(loss_id), float(momentum), int(ds.intercept_row),
-                int(epochs), tbits, mbits, *l1_args,
-            )
-        else:
-            for epoch in range(epochs):
-                lr_scale = 1.0 / (1.0 + lr_decay * epoch)
-                ext.sgd_epoch_bits(
-                    Xs, XsT, GT, W, V, WbfT, partial, ys, folds,
-                    cls_p, cfold_p, cls2_p, lr_p, l2_p, fmask, rw_t,
-                    inv_m, bs, int(loss_id), float(lr_scale),
-                    float(momentum), int(ds.intercept_row),
-                    tbits, mbits, *l1_args,
-                )
-    elif col_l1 is not None:
+    l1_args = ()
+    if col_l1 is not None:
         if not 0.0 <= momentum < 1.0:
             raise ValueError("the L1 update needs momentum in [0, 1)")
-        l1_p = pad_cols(col_l1, 0.0)
-        cpos = torch.zeros_like(W)
-        cneg = torch.zeros_like(W)
-        if lr_decay == 0.0:
-            ext.sgd_solve_l1(
-                Xs, XsT, GT, W, V, WbfT, partial, ys, folds,
-                cls_p, cfold_p, cls2_p, lr_p, l2_p, fmask, rw_t, inv_m,
-                bs, int(loss_id), float(momentum), int(ds.intercept_row),
-                int(epochs), l1_p, cpos, cneg, gk_arg,
-            )
-        else:
-            for epoch in range(epochs):
-                lr_scale = 1.0 / (1.0 + lr_decay * epoch)
-                ext.sgd_epoch_l1(
-                    Xs, XsT, GT, W, V, WbfT, partial, ys, folds,
-                    cls_p, cfold_p, cls2_p, lr_p, l2_p, fmask, rw_t,
-                    inv_m, bs, int(loss_id), float(lr_scale),
-                    float(momentum), int(ds.intercept_row),
-                    l1_p, cpos, cneg, gk_arg,
-                )
-    elif lr_decay == 0.0:
+        l1_args = (pad_cols(col_l1, 0.0), torch.zeros_like(W),
+                   torch.zeros_like(W))
+    # the entry and what it takes after the arguments all entries share:
+    # *_bits takes the planes and the optional L1 state, *_l1 the L1 state
+    # and the group width, the plain one the group width
+    if tbits is not None:
+        kind, tail = "_bits", (tbits, mbits, *l1_args)
+    elif col_l1 is not None:
+        kind, tail = "_l1", (*l1_args, gk_arg)
+    else:
+        kind, tail = "", (gk_arg,)
+    head = (Xs, XsT, GT, W, V, WbfT, partial, ys, folds, cls_p, cfold_p,
+            cls2_p, lr_p, l2_p, fmask, rw_t, inv_m)
+    if lr_decay == 0.0:
         # constant lr_scale: every epoch launches the identical
         # sequence — one C++ call, epochs 2..N replay a hipGraph
-        ext.sgd_solve(
-            Xs, XsT, GT, W, V, WbfT, partial, ys, folds,
-            cls_p, cfold_p, cls2_p, lr_p, l2_p, fmask, rw_t, inv_m,
-            bs, int(loss_id), float(momentum), int(ds.intercept_row),
-            int(epochs), gk_arg,
-        )
+        getattr(ext, "sgd_solve" + kind)(
+            *head, bs, int(loss_id), float(momentum),
+            int(ds.intercept_row), int(epochs), *tail)
     else:
+        epoch_fn = getattr(ext, "sgd_epoch" + kind)
         for epoch in range(epochs):
             lr_scale = 1.0 / (1.0 + lr_decay * epoch)
-            ext.sgd_epoch(
-                Xs, XsT, GT, W, V, WbfT, partial, ys, folds,
-                cls_p, cfold_p, cls2_p, lr_p, l2_p, fmask, rw_t, inv_m,
-                bs, int(loss_id), float(lr_scale), float(momentum),
-                int(ds.intercept_row), gk_arg,
-            )
+            epoch_fn(
+                *head, bs, int(loss_id), float(lr_scale), float(momentum),
+                int(ds.intercept_row), *tail)
     if place is not None:
         return W.index_select(1, place)
     return W[:, :ncols]

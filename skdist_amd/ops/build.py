@@ -58,7 +58,8 @@ def build(verbose=True):
         "hipcc", f"--offload-arch={ARCH}", "-O3", "-std=c++17", "-fPIC",
         "-Wall", "-Wno-unused-function",
     ]
-    headers = [os.path.join(CSRC, h) for h in ("common.h", "tree_api.h")]
+    headers = [os.path.join(CSRC, h) for h in ("common.h", "sgd_api.h",
+                                               "tree_api.h")]
     for src in KERNEL_SOURCES:
         path = os.path.join(CSRC, src)
         if not os.path.exists(path):

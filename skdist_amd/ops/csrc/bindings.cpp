@@ -7,55 +7,8 @@
 
 #include <optional>
 
+#include "sgd_api.h"
 #include "tree_api.h"
-
-extern "C" hipError_t skdist_sgd_step(
-    const void* Xs, const void* XsT, const void* WbfT_in,
-    void* GT, void* W, void* V, void* WbfT, void* partial,
-    const void* y, const void* fold,
-    const void* col_class, const void* col_fold, const void* col_class2,
-    const void* col_lr, const void* col_l2, const void* fmask,
-    const void* row_w, float inv_m,
-    long long start, long long m, long long n, long long n_pad,
-    long long fa_store, int fa, int ncols_pad,
-    int gt_stride, int splitk, int loss_id,
-    float lr_scale, float momentum, int intercept_row, int group_k,
-    hipStream_t stream);
-// same step with the cumulative-penalty L1 update (k_reduce_update_l1)
-extern "C" hipError_t skdist_sgd_step_l1(
-    const void* Xs, const void* XsT, const void* WbfT_in,
-    void* GT, void* W, void* V, void* WbfT, void* partial,
-    const void* y, const void* fold,
-    const void* col_class, const void* col_fold, const void* col_class2,
-    const void* col_lr, const void* col_l2, const void* fmask,
-    const void* row_w, float inv_m,
-    long long start, long long m, long long n, long long n_pad,
-    long long fa_store, int fa, int ncols_pad,
-    int gt_stride, int splitk, int loss_id,
-    float lr_scale, float momentum, int intercept_row,
-    const void* col_l1, void* cpos, void* cneg, int group_k,
-    hipStream_t stream);
-// same step with per-element targets from bit planes (k_fwd_gt_bits as K1);
-// col_l1 null is the L2-only update, Mbits null means every element trains
-extern "C" hipError_t skdist_sgd_step_bits(
-    const void* Xs, const void* XsT, const void* WbfT_in,
-    void* GT, void* W, void* V, void* WbfT, void* partial,
-    const void* y, const void* fold,
-    const void* col_class, const void* col_fold, const void* col_class2,
-    const void* col_lr, const void* col_l2, const void* fmask,
-    const void* row_w, float inv_m,
-    long long start, long long m, long long n, long long n_pad,
-    long long fa_store, int fa, int ncols_pad,
-    int gt_stride, int splitk, int loss_id,
-    float lr_scale, float momentum, int intercept_row,
-    const void* col_l1, void* cpos, void* cneg,
-    const void* Tbits, const void* Mbits, hipStream_t stream);
-// K2 alone; variant: 0 the launcher's rule, 1 / 2 the 128- / 96-row tile,
-// 3 the whole-fa kernel
-extern "C" hipError_t skdist_grad_partial(
-    const void* XsT, const void* GT, void* partial, long long start,
-    long long m, long long n_pad, long long fa_store, int fa, int ncols_pad,
-    int gt_stride, int splitk, int variant, hipStream_t stream);
 
 namespace {
 
@@ -85,17 +38,15 @@ void check_2d(const torch::Tensor& t, torch::ScalarType dt, int64_t rows,
                 name, " must be [", rows, ", ", cols, "]");
 }
 
-struct StepArgs {
-    int64_t n_pad, fa, fa_store, ncols_pad, gt_stride, splitk, n;
-};
-
 // Every tensor of one dense SGD step (K1+K2+K3), checked against what the
 // kernels index: shared by sgd_step and the epoch / solve entries with and
 // without L1.  `rows` is the largest row count one step covers (m for
 // sgd_step, the batch size otherwise); V, fmask and row_w may be empty.
 // loss_id 3 (softmax) trains groups of group_k columns (2..128) with
-// k_fwd_gt_softmax; every other loss takes group_k == 0.
-StepArgs check_step_tensors(
+// k_fwd_gt_softmax; every other loss takes group_k == 0.  Returns the step
+// with every pointer and dimension set; the batch (start, m, inv_m) and
+// lr_scale are the caller's.
+SgdStep check_step_tensors(
     const torch::Tensor& Xs, const torch::Tensor& XsT,
     const torch::Tensor& GT, const torch::Tensor& W, const torch::Tensor& V,
     const torch::Tensor& WbfT, const torch::Tensor& partial,
@@ -125,59 +76,82 @@ StepArgs check_step_tensors(
     TORCH_CHECK(Xs.dim() == 2 && XsT.dim() == 2 && GT.dim() == 2 &&
                 W.dim() == 2, "Xs, XsT, GT and W must be 2-D");
     TORCH_CHECK(partial.dim() == 3, "partial must be [splitk, fa, ncols_pad]");
-    StepArgs a;
-    a.n_pad = Xs.size(0);
-    a.fa = Xs.size(1);
-    a.fa_store = XsT.size(0);
-    a.ncols_pad = W.size(1);
-    a.gt_stride = GT.size(1);
-    a.splitk = partial.size(0);
-    a.n = y.numel();
-    TORCH_CHECK(a.fa >= 32 && a.fa % 32 == 0,
-                "fa must be a multiple of 32");
-    TORCH_CHECK(a.n_pad >= 128 && a.n_pad % 128 == 0,
+    const int64_t n_pad = Xs.size(0), fa = Xs.size(1);
+    const int64_t fa_store = XsT.size(0), ncols_pad = W.size(1);
+    const int64_t gt_stride = GT.size(1), splitk = partial.size(0);
+    const int64_t n = y.numel();
+    TORCH_CHECK(fa >= 32 && fa % 32 == 0, "fa must be a multiple of 32");
+    TORCH_CHECK(n_pad >= 128 && n_pad % 128 == 0,
                 "n_pad must be a multiple of 128");
-    TORCH_CHECK(a.fa_store % 128 == 0, "fa_store must be a multiple of 128");
-    TORCH_CHECK(a.fa_store >= a.fa, "XsT must have at least fa rows");
-    TORCH_CHECK(a.ncols_pad >= 128 && a.ncols_pad % 128 == 0,
+    TORCH_CHECK(fa_store % 128 == 0, "fa_store must be a multiple of 128");
+    TORCH_CHECK(fa_store >= fa, "XsT must have at least fa rows");
+    TORCH_CHECK(ncols_pad >= 128 && ncols_pad % 128 == 0,
                 "ncols_pad must be a mult of 128");
-    TORCH_CHECK(XsT.size(1) == a.n_pad, "XsT shape mismatch");
-    TORCH_CHECK(W.size(0) == a.fa, "W rows != fa");
-    TORCH_CHECK(a.splitk >= 1, "splitk must be >= 1");
-    TORCH_CHECK(partial.size(1) == a.fa && partial.size(2) == a.ncols_pad,
+    TORCH_CHECK(XsT.size(1) == n_pad, "XsT shape mismatch");
+    TORCH_CHECK(W.size(0) == fa, "W rows != fa");
+    TORCH_CHECK(splitk >= 1, "splitk must be >= 1");
+    TORCH_CHECK(partial.size(1) == fa && partial.size(2) == ncols_pad,
                 "partial must be [splitk, fa, ncols_pad]");
-    check_2d(WbfT, bf16, a.ncols_pad, a.fa, "WbfT");
+    check_2d(WbfT, bf16, ncols_pad, fa, "WbfT");
     TORCH_CHECK(rows >= 1, "a step needs at least one row");
     const int64_t rows_pad = (rows + 127) / 128 * 128;
-    TORCH_CHECK(GT.size(0) == a.ncols_pad && a.gt_stride >= rows_pad &&
-                a.gt_stride % 8 == 0,
+    TORCH_CHECK(GT.size(0) == ncols_pad && gt_stride >= rows_pad &&
+                gt_stride % 8 == 0,
                 "GT must be [ncols_pad, gt_stride >= ", rows_pad,
                 "] with gt_stride a multiple of 8");
-    TORCH_CHECK(a.n >= 1 && a.n <= a.n_pad, "y must have 1..n_pad elements");
-    check_vec(y, f32, a.n, "y");
-    check_vec(fold, i32, a.n, "fold");
-    check_vec(col_class, i32, a.ncols_pad, "col_class");
-    check_vec(col_fold, i32, a.ncols_pad, "col_fold");
-    check_vec(col_class2, i32, a.ncols_pad, "col_class2");
-    check_vec(col_lr, f32, a.ncols_pad, "col_lr");
-    check_vec(col_l2, f32, a.ncols_pad, "col_l2");
-    if (row_w.numel() > 0) check_vec(row_w, f32, a.n, "row_w");
+    TORCH_CHECK(n >= 1 && n <= n_pad, "y must have 1..n_pad elements");
+    check_vec(y, f32, n, "y");
+    check_vec(fold, i32, n, "fold");
+    check_vec(col_class, i32, ncols_pad, "col_class");
+    check_vec(col_fold, i32, ncols_pad, "col_fold");
+    check_vec(col_class2, i32, ncols_pad, "col_class2");
+    check_vec(col_lr, f32, ncols_pad, "col_lr");
+    check_vec(col_l2, f32, ncols_pad, "col_l2");
+    if (row_w.numel() > 0) check_vec(row_w, f32, n, "row_w");
     if (fmask.numel() > 0)
-        check_2d(fmask, torch::kUInt8, a.fa, a.ncols_pad, "fmask");
+        check_2d(fmask, torch::kUInt8, fa, ncols_pad, "fmask");
     if (V.numel() > 0) {
         check_t(V, f32, "V");
         TORCH_CHECK(V.sizes() == W.sizes(), "V must be empty or match W");
     } else {
         TORCH_CHECK(!(momentum > 0.0), "momentum > 0 needs V");
     }
-    TORCH_CHECK(intercept_row >= 0 && intercept_row < a.fa,
+    TORCH_CHECK(intercept_row >= 0 && intercept_row < fa,
                 "intercept_row must be in [0, fa)");
-    return a;
+    SgdStep s;
+    s.Xs = Xs.data_ptr();
+    s.XsT = XsT.data_ptr();
+    s.GT = GT.data_ptr();
+    s.W = W.data_ptr();
+    s.V = V.numel() ? V.data_ptr() : nullptr;
+    s.WbfT = WbfT.data_ptr();
+    s.partial = partial.data_ptr();
+    s.y = y.data_ptr();
+    s.fold = fold.data_ptr();
+    s.col_class = col_class.data_ptr();
+    s.col_fold = col_fold.data_ptr();
+    s.col_class2 = col_class2.data_ptr();
+    s.col_lr = col_lr.data_ptr();
+    s.col_l2 = col_l2.data_ptr();
+    s.fmask = fmask.numel() ? fmask.data_ptr() : nullptr;
+    s.row_w = row_w.numel() ? row_w.data_ptr() : nullptr;
+    s.n = n;
+    s.n_pad = n_pad;
+    s.fa_store = fa_store;
+    s.fa = (int)fa;
+    s.ncols_pad = (int)ncols_pad;
+    s.gt_stride = (int)gt_stride;
+    s.splitk = (int)splitk;
+    s.loss_id = (int)loss_id;
+    s.momentum = (float)momentum;
+    s.intercept_row = (int)intercept_row;
+    s.group_k = (int)group_k;
+    return s;
 }
 
 // the epoch / solve entries walk y in batches of batch_size rows and read
 // one 1/m (or 1/sum(w)) per batch from a CPU f32 tensor
-void check_batches(const StepArgs& a, int64_t batch_size,
+void check_batches(const SgdStep& s, int64_t batch_size,
                    const torch::Tensor& inv_m_cpu) {
     TORCH_CHECK(batch_size >= 128 && batch_size % 128 == 0,
                 "batch_size must be a mult of 128");
@@ -185,46 +159,86 @@ void check_batches(const StepArgs& a, int64_t batch_size,
     TORCH_CHECK(inv_m_cpu.scalar_type() == torch::kFloat32 &&
                 inv_m_cpu.is_contiguous(),
                 "inv_m must be a contiguous f32 tensor");
-    TORCH_CHECK(inv_m_cpu.numel() >= (a.n + batch_size - 1) / batch_size,
+    TORCH_CHECK(inv_m_cpu.numel() >= (s.n + batch_size - 1) / batch_size,
                 "inv_m shorter than the batch count");
 }
 
-void sgd_step(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
-              torch::Tensor W, torch::Tensor V, torch::Tensor WbfT,
-              torch::Tensor partial, torch::Tensor y, torch::Tensor fold,
-              torch::Tensor col_class, torch::Tensor col_fold,
-              torch::Tensor col_class2,
-              torch::Tensor col_lr, torch::Tensor col_l2,
-              torch::Tensor fmask, torch::Tensor row_w,
-              int64_t start, int64_t m, int64_t loss_id, double lr_scale,
-              double momentum, int64_t intercept_row, double inv_m,
-              int64_t group_k) {
-    TORCH_CHECK(m >= 1, "m must be >= 1");
-    auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
-                                col_class, col_fold, col_class2, col_lr,
-                                col_l2, fmask, row_w, m, momentum,
-                                intercept_row, loss_id, group_k);
+// the batch of sgd_step / sgd_step_bits is the caller's
+void set_batch(SgdStep& s, int64_t start, int64_t m, double inv_m,
+               double lr_scale) {
     // K2 stages 16 B chunks of XsT from column `start` on
     TORCH_CHECK(start >= 0 && start % 8 == 0,
                 "start must be a non-negative multiple of 8");
-    TORCH_CHECK(start + (m + 127) / 128 * 128 <= a.n_pad,
+    TORCH_CHECK(start + (m + 127) / 128 * 128 <= s.n_pad,
                 "start + m_pad must be <= n_pad");
-    const bool has_V = V.numel() > 0;
-    auto stream = c10::hip::getCurrentHIPStream().stream();
-    hipError_t err = skdist_sgd_step(
-        Xs.data_ptr(), XsT.data_ptr(), WbfT.data_ptr(), GT.data_ptr(),
-        W.data_ptr(), has_V ? V.data_ptr() : nullptr, WbfT.data_ptr(),
-        partial.data_ptr(), y.data_ptr(), fold.data_ptr(),
-        col_class.data_ptr(), col_fold.data_ptr(), col_class2.data_ptr(),
-        col_lr.data_ptr(), col_l2.data_ptr(),
-        fmask.numel() ? fmask.data_ptr() : nullptr,
-        row_w.numel() ? row_w.data_ptr() : nullptr, (float)inv_m,
-        start, m, a.n, a.n_pad, a.fa_store, (int)a.fa,
-        (int)a.ncols_pad, (int)a.gt_stride, (int)a.splitk, (int)loss_id,
-        (float)lr_scale, (float)momentum, (int)intercept_row, (int)group_k,
-        stream);
-    TORCH_CHECK(err == hipSuccess, "skdist_sgd_step: ",
-                hipGetErrorString(err));
+    s.start = start;
+    s.m = m;
+    s.inv_m = (float)inv_m;
+    s.lr_scale = (float)lr_scale;
+}
+
+// the L1 state of a step: per-column coefficient plus the two per-weight
+// credit tables, all-or-nothing
+void check_l1(SgdStep& s, torch::Tensor& col_l1, torch::Tensor& cpos,
+              torch::Tensor& cneg, torch::Tensor& W, double momentum) {
+    for (auto* t : {&col_l1, &cpos, &cneg}) {
+        CHECK_DEV(*t);
+        CHECK_CONT(*t);
+        TORCH_CHECK(t->scalar_type() == torch::kFloat32, "L1 state is f32");
+    }
+    TORCH_CHECK(col_l1.numel() == W.size(1), "col_l1 must be [ncols_pad]");
+    TORCH_CHECK(cpos.sizes() == W.sizes() && cneg.sizes() == W.sizes(),
+                "L1 credit tables must match W");
+    TORCH_CHECK(momentum >= 0.0 && momentum < 1.0,
+                "momentum must be in [0, 1)");
+    s.col_l1 = col_l1.data_ptr();
+    s.cpos = cpos.data_ptr();
+    s.cneg = cneg.data_ptr();
+}
+
+// the optional L1 tensors of the *_bits entries: all three empty is the
+// L2-only update
+void check_l1_opt(SgdStep& s, torch::Tensor& col_l1, torch::Tensor& cpos,
+                  torch::Tensor& cneg, torch::Tensor& W, double momentum) {
+    if (col_l1.numel() == 0 && cpos.numel() == 0 && cneg.numel() == 0)
+        return;
+    TORCH_CHECK(col_l1.numel() > 0 && cpos.numel() > 0 && cneg.numel() > 0,
+                "col_l1, cpos and cneg (the L1 state) go together");
+    check_l1(s, col_l1, cpos, cneg, W, momentum);
+}
+
+// the bit planes of a step with per-element targets: Tbits and, optionally,
+// Mbits, both int32 [n_pad, ncols_pad / 32]
+void check_bits(SgdStep& s, const torch::Tensor& tbits,
+                const torch::Tensor& mbits, int64_t loss_id) {
+    TORCH_CHECK(loss_id != 3,
+                "per-element targets do not go with the softmax loss");
+    check_2d(tbits, torch::kInt32, s.n_pad, s.ncols_pad / 32, "tbits");
+    s.Tbits = tbits.data_ptr();
+    if (mbits.numel() > 0) {
+        check_2d(mbits, torch::kInt32, s.n_pad, s.ncols_pad / 32, "mbits");
+        s.Mbits = mbits.data_ptr();
+    }
+}
+
+void launch_step(const SgdStep& s, const char* who) {
+    hipError_t err =
+        skdist_sgd_step(s, c10::hip::getCurrentHIPStream().stream());
+    TORCH_CHECK(err == hipSuccess, who, ": ", hipGetErrorString(err));
+}
+
+// every mini-batch step of one epoch on `st`
+void enqueue_epoch(SgdStep s, const float* inv_p, int64_t batch_size,
+                   hipStream_t st, const char* who) {
+    const int64_t n = s.n;
+    int64_t bi = 0;
+    for (int64_t start = 0; start < n; start += batch_size, ++bi) {
+        s.start = start;
+        s.m = std::min(batch_size, n - start);
+        s.inv_m = inv_p[bi];
+        hipError_t err = skdist_sgd_step(s, st);
+        TORCH_CHECK(err == hipSuccess, who, ": ", hipGetErrorString(err));
+    }
 }
 
 // K2 of one step on its own (tests, timing under a kernel trace): the
@@ -332,130 +346,35 @@ static void run_epochs_graphed(int64_t epochs, hipStream_t torch_stream,
     hipStreamDestroy(s2);
 }
 
-// L1 state of one dense solve: per-column coefficient plus the two
-// per-weight credit tables, all-or-nothing
-struct L1Args {
-    const void* col_l1 = nullptr;
-    void* cpos = nullptr;
-    void* cneg = nullptr;
-};
-
-L1Args check_l1(torch::Tensor& col_l1, torch::Tensor& cpos,
-                torch::Tensor& cneg, torch::Tensor& W, double momentum) {
-    for (auto* t : {&col_l1, &cpos, &cneg}) {
-        CHECK_DEV(*t);
-        CHECK_CONT(*t);
-        TORCH_CHECK(t->scalar_type() == torch::kFloat32, "L1 state is f32");
-    }
-    TORCH_CHECK(col_l1.numel() == W.size(1), "col_l1 must be [ncols_pad]");
-    TORCH_CHECK(cpos.sizes() == W.sizes() && cneg.sizes() == W.sizes(),
-                "L1 credit tables must match W");
-    TORCH_CHECK(momentum >= 0.0 && momentum < 1.0,
-                "momentum must be in [0, 1)");
-    L1Args l1;
-    l1.col_l1 = col_l1.data_ptr();
-    l1.cpos = cpos.data_ptr();
-    l1.cneg = cneg.data_ptr();
-    return l1;
+// all epochs of a solve; lr_scale is constant (lr_decay=0), so every epoch
+// launches the identical sequence -> hipGraph replay
+void solve_epochs(const SgdStep& s, const torch::Tensor& inv_m_cpu,
+                  int64_t batch_size, int64_t epochs, const char* who) {
+    const float* inv_p = (const float*)inv_m_cpu.data_ptr();
+    auto body = [&](hipStream_t st) {
+        enqueue_epoch(s, inv_p, batch_size, st, who);
+    };
+    run_epochs_graphed(epochs, c10::hip::getCurrentHIPStream().stream(),
+                       body);
 }
 
-// the bit planes of a solve with per-element targets: Tbits and, optionally,
-// Mbits, both int32 [n_pad, ncols_pad / 32]; tbits == nullptr is a solve
-// with class targets
-struct BitArgs {
-    const void* tbits = nullptr;
-    const void* mbits = nullptr;
-};
-
-BitArgs check_bits(const StepArgs& a, const torch::Tensor& tbits,
-                   const torch::Tensor& mbits, int64_t loss_id) {
-    TORCH_CHECK(loss_id != 3,
-                "per-element targets do not go with the softmax loss");
-    check_2d(tbits, torch::kInt32, a.n_pad, a.ncols_pad / 32, "tbits");
-    BitArgs b;
-    b.tbits = tbits.data_ptr();
-    if (mbits.numel() > 0) {
-        check_2d(mbits, torch::kInt32, a.n_pad, a.ncols_pad / 32, "mbits");
-        b.mbits = mbits.data_ptr();
-    }
-    return b;
-}
-
-// the optional L1 tensors of the *_bits entries: all three empty is the
-// L2-only update
-L1Args check_l1_opt(torch::Tensor& col_l1, torch::Tensor& cpos,
-                    torch::Tensor& cneg, torch::Tensor& W, double momentum) {
-    if (col_l1.numel() == 0 && cpos.numel() == 0 && cneg.numel() == 0)
-        return L1Args{};
-    TORCH_CHECK(col_l1.numel() > 0 && cpos.numel() > 0 && cneg.numel() > 0,
-                "col_l1, cpos and cneg (the L1 state) go together");
-    return check_l1(col_l1, cpos, cneg, W, momentum);
-}
-
-// every mini-batch step of one epoch on `st`; `l1.col_l1 == nullptr`
-// launches the L2-only step, `bits.tbits != nullptr` the step with
-// per-element targets
-void enqueue_epoch(const StepArgs& a, torch::Tensor& Xs, torch::Tensor& XsT,
-                   torch::Tensor& GT, torch::Tensor& W, torch::Tensor& V,
-                   torch::Tensor& WbfT, torch::Tensor& partial,
-                   torch::Tensor& y, torch::Tensor& fold,
-                   torch::Tensor& col_class, torch::Tensor& col_fold,
-                   torch::Tensor& col_class2, torch::Tensor& col_lr,
-                   torch::Tensor& col_l2, torch::Tensor& fmask,
-                   torch::Tensor& row_w, const float* inv_p,
-                   int64_t batch_size, int64_t loss_id, float lr_scale,
-                   double momentum, int64_t intercept_row,
-                   const L1Args& l1, int64_t group_k, hipStream_t st,
-                   const char* who, const BitArgs& bits = BitArgs{}) {
-    const bool has_V = V.numel() > 0;
-    int64_t bi = 0;
-    for (int64_t start = 0; start < a.n; start += batch_size, ++bi) {
-        const int64_t m = std::min(batch_size, a.n - start);
-        void* Vp = has_V ? V.data_ptr() : nullptr;
-        const void* fm = fmask.numel() ? fmask.data_ptr() : nullptr;
-        const void* rw = row_w.numel() ? row_w.data_ptr() : nullptr;
-        hipError_t err;
-        if (bits.tbits != nullptr) {
-            err = skdist_sgd_step_bits(
-                Xs.data_ptr(), XsT.data_ptr(), WbfT.data_ptr(),
-                GT.data_ptr(), W.data_ptr(), Vp, WbfT.data_ptr(),
-                partial.data_ptr(), y.data_ptr(), fold.data_ptr(),
-                col_class.data_ptr(), col_fold.data_ptr(),
-                col_class2.data_ptr(), col_lr.data_ptr(),
-                col_l2.data_ptr(), fm, rw, inv_p[bi],
-                start, m, a.n, a.n_pad, a.fa_store,
-                (int)a.fa, (int)a.ncols_pad, (int)a.gt_stride,
-                (int)a.splitk, (int)loss_id, lr_scale, (float)momentum,
-                (int)intercept_row, l1.col_l1, l1.cpos, l1.cneg,
-                bits.tbits, bits.mbits, st);
-        } else if (l1.col_l1 == nullptr) {
-            err = skdist_sgd_step(
-                Xs.data_ptr(), XsT.data_ptr(), WbfT.data_ptr(),
-                GT.data_ptr(), W.data_ptr(), Vp, WbfT.data_ptr(),
-                partial.data_ptr(), y.data_ptr(), fold.data_ptr(),
-                col_class.data_ptr(), col_fold.data_ptr(),
-                col_class2.data_ptr(), col_lr.data_ptr(),
-                col_l2.data_ptr(), fm, rw, inv_p[bi],
-                start, m, a.n, a.n_pad, a.fa_store,
-                (int)a.fa, (int)a.ncols_pad, (int)a.gt_stride,
-                (int)a.splitk, (int)loss_id, lr_scale, (float)momentum,
-                (int)intercept_row, (int)group_k, st);
-        } else {
-            err = skdist_sgd_step_l1(
-                Xs.data_ptr(), XsT.data_ptr(), WbfT.data_ptr(),
-                GT.data_ptr(), W.data_ptr(), Vp, WbfT.data_ptr(),
-                partial.data_ptr(), y.data_ptr(), fold.data_ptr(),
-                col_class.data_ptr(), col_fold.data_ptr(),
-                col_class2.data_ptr(), col_lr.data_ptr(),
-                col_l2.data_ptr(), fm, rw, inv_p[bi],
-                start, m, a.n, a.n_pad, a.fa_store,
-                (int)a.fa, (int)a.ncols_pad, (int)a.gt_stride,
-                (int)a.splitk, (int)loss_id, lr_scale, (float)momentum,
-                (int)intercept_row, l1.col_l1, l1.cpos, l1.cneg,
-                (int)group_k, st);
-        }
-        TORCH_CHECK(err == hipSuccess, who, ": ", hipGetErrorString(err));
-    }
+void sgd_step(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
+              torch::Tensor W, torch::Tensor V, torch::Tensor WbfT,
+              torch::Tensor partial, torch::Tensor y, torch::Tensor fold,
+              torch::Tensor col_class, torch::Tensor col_fold,
+              torch::Tensor col_class2,
+              torch::Tensor col_lr, torch::Tensor col_l2,
+              torch::Tensor fmask, torch::Tensor row_w,
+              int64_t start, int64_t m, int64_t loss_id, double lr_scale,
+              double momentum, int64_t intercept_row, double inv_m,
+              int64_t group_k) {
+    TORCH_CHECK(m >= 1, "m must be >= 1");
+    auto s = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+                                col_class, col_fold, col_class2, col_lr,
+                                col_l2, fmask, row_w, m, momentum,
+                                intercept_row, loss_id, group_k);
+    set_batch(s, start, m, inv_m, lr_scale);
+    launch_step(s, "skdist_sgd_step");
 }
 
 // one whole epoch: the minibatch loop runs in C++ so the hot path costs
@@ -470,21 +389,17 @@ void sgd_epoch(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                torch::Tensor inv_m_cpu,  // [n_batches] f32 on CPU
                int64_t batch_size, int64_t loss_id, double lr_scale,
                double momentum, int64_t intercept_row, int64_t group_k) {
-    auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+    auto s = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
                                 col_class, col_fold, col_class2, col_lr,
                                 col_l2, fmask, row_w, batch_size, momentum,
                                 intercept_row, loss_id, group_k);
-    check_batches(a, batch_size, inv_m_cpu);
-    enqueue_epoch(a, Xs, XsT, GT, W, V, WbfT, partial, y, fold, col_class,
-                  col_fold, col_class2, col_lr, col_l2, fmask, row_w,
-                  (const float*)inv_m_cpu.data_ptr(), batch_size, loss_id,
-                  (float)lr_scale, momentum, intercept_row, L1Args{},
-                  group_k, c10::hip::getCurrentHIPStream().stream(),
-                  "sgd_epoch");
+    check_batches(s, batch_size, inv_m_cpu);
+    s.lr_scale = (float)lr_scale;
+    enqueue_epoch(s, (const float*)inv_m_cpu.data_ptr(), batch_size,
+                  c10::hip::getCurrentHIPStream().stream(), "sgd_epoch");
 }
 
-// all epochs in one call; lr_scale is constant (lr_decay=0), so every
-// epoch launches the identical sequence -> hipGraph replay
+// all epochs in one call (solve_epochs)
 void sgd_solve(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                torch::Tensor W, torch::Tensor V, torch::Tensor WbfT,
                torch::Tensor partial, torch::Tensor y, torch::Tensor fold,
@@ -495,21 +410,12 @@ void sgd_solve(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                torch::Tensor inv_m_cpu, int64_t batch_size,
                int64_t loss_id, double momentum, int64_t intercept_row,
                int64_t epochs, int64_t group_k) {
-    auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+    auto s = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
                                 col_class, col_fold, col_class2, col_lr,
                                 col_l2, fmask, row_w, batch_size, momentum,
                                 intercept_row, loss_id, group_k);
-    check_batches(a, batch_size, inv_m_cpu);
-    const float* inv_p = (const float*)inv_m_cpu.data_ptr();
-    auto torch_stream = c10::hip::getCurrentHIPStream().stream();
-    auto body = [&](hipStream_t st) {
-        enqueue_epoch(a, Xs, XsT, GT, W, V, WbfT, partial, y, fold,
-                      col_class, col_fold, col_class2, col_lr, col_l2,
-                      fmask, row_w, inv_p, batch_size, loss_id, 1.0f,
-                      momentum, intercept_row, L1Args{}, group_k, st,
-                      "sgd_solve");
-    };
-    run_epochs_graphed(epochs, torch_stream, body);
+    check_batches(s, batch_size, inv_m_cpu);
+    solve_epochs(s, inv_m_cpu, batch_size, epochs, "sgd_solve");
 }
 
 // L1 / elastic-net twins of sgd_epoch and sgd_solve: same positional
@@ -517,56 +423,46 @@ void sgd_solve(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
 // [fa][ncols_pad] (zero-initialised by the caller, carried across epochs)
 void sgd_epoch_l1(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                   torch::Tensor W, torch::Tensor V, torch::Tensor WbfT,
-                  torch::Tensor partial, torch::Tensor y,
-                  torch::Tensor fold, torch::Tensor col_class,
-                  torch::Tensor col_fold, torch::Tensor col_class2,
+                  torch::Tensor partial, torch::Tensor y, torch::Tensor fold,
+                  torch::Tensor col_class, torch::Tensor col_fold,
+                  torch::Tensor col_class2,
                   torch::Tensor col_lr, torch::Tensor col_l2,
                   torch::Tensor fmask, torch::Tensor row_w,
-                  torch::Tensor inv_m_cpu, int64_t batch_size,
-                  int64_t loss_id, double lr_scale, double momentum,
-                  int64_t intercept_row, torch::Tensor col_l1,
+                  torch::Tensor inv_m_cpu,  // [n_batches] f32 on CPU
+                  int64_t batch_size, int64_t loss_id, double lr_scale,
+                  double momentum, int64_t intercept_row, torch::Tensor col_l1,
                   torch::Tensor cpos, torch::Tensor cneg,
                   int64_t group_k) {
-    auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+    auto s = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
                                 col_class, col_fold, col_class2, col_lr,
                                 col_l2, fmask, row_w, batch_size, momentum,
                                 intercept_row, loss_id, group_k);
-    check_batches(a, batch_size, inv_m_cpu);
-    auto l1 = check_l1(col_l1, cpos, cneg, W, momentum);
-    enqueue_epoch(a, Xs, XsT, GT, W, V, WbfT, partial, y, fold, col_class,
-                  col_fold, col_class2, col_lr, col_l2, fmask, row_w,
-                  (const float*)inv_m_cpu.data_ptr(), batch_size, loss_id,
-                  (float)lr_scale, momentum, intercept_row, l1, group_k,
+    check_batches(s, batch_size, inv_m_cpu);
+    check_l1(s, col_l1, cpos, cneg, W, momentum);
+    s.lr_scale = (float)lr_scale;
+    enqueue_epoch(s, (const float*)inv_m_cpu.data_ptr(), batch_size,
                   c10::hip::getCurrentHIPStream().stream(), "sgd_epoch_l1");
 }
 
 void sgd_solve_l1(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                   torch::Tensor W, torch::Tensor V, torch::Tensor WbfT,
-                  torch::Tensor partial, torch::Tensor y,
-                  torch::Tensor fold, torch::Tensor col_class,
-                  torch::Tensor col_fold, torch::Tensor col_class2,
+                  torch::Tensor partial, torch::Tensor y, torch::Tensor fold,
+                  torch::Tensor col_class, torch::Tensor col_fold,
+                  torch::Tensor col_class2,
                   torch::Tensor col_lr, torch::Tensor col_l2,
                   torch::Tensor fmask, torch::Tensor row_w,
                   torch::Tensor inv_m_cpu, int64_t batch_size,
                   int64_t loss_id, double momentum, int64_t intercept_row,
-                  int64_t epochs, torch::Tensor col_l1, torch::Tensor cpos,
-                  torch::Tensor cneg, int64_t group_k) {
-    auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+                  int64_t epochs, torch::Tensor col_l1,
+                  torch::Tensor cpos, torch::Tensor cneg,
+                  int64_t group_k) {
+    auto s = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
                                 col_class, col_fold, col_class2, col_lr,
                                 col_l2, fmask, row_w, batch_size, momentum,
                                 intercept_row, loss_id, group_k);
-    check_batches(a, batch_size, inv_m_cpu);
-    auto l1 = check_l1(col_l1, cpos, cneg, W, momentum);
-    const float* inv_p = (const float*)inv_m_cpu.data_ptr();
-    auto torch_stream = c10::hip::getCurrentHIPStream().stream();
-    auto body = [&](hipStream_t st) {
-        enqueue_epoch(a, Xs, XsT, GT, W, V, WbfT, partial, y, fold,
-                      col_class, col_fold, col_class2, col_lr, col_l2,
-                      fmask, row_w, inv_p, batch_size, loss_id, 1.0f,
-                      momentum, intercept_row, l1, group_k, st,
-                      "sgd_solve_l1");
-    };
-    run_epochs_graphed(epochs, torch_stream, body);
+    check_batches(s, batch_size, inv_m_cpu);
+    check_l1(s, col_l1, cpos, cneg, W, momentum);
+    solve_epochs(s, inv_m_cpu, batch_size, epochs, "sgd_solve_l1");
 }
 
 // ---- per-element targets (k_fwd_gt_bits as K1): the argument lists of
@@ -575,101 +471,73 @@ void sgd_solve_l1(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
 // L1 tensors col_l1, cpos, cneg (all empty: the L2-only update)
 void sgd_step_bits(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                    torch::Tensor W, torch::Tensor V, torch::Tensor WbfT,
-                   torch::Tensor partial, torch::Tensor y,
-                   torch::Tensor fold, torch::Tensor col_class,
-                   torch::Tensor col_fold, torch::Tensor col_class2,
+                   torch::Tensor partial, torch::Tensor y, torch::Tensor fold,
+                   torch::Tensor col_class, torch::Tensor col_fold,
+                   torch::Tensor col_class2,
                    torch::Tensor col_lr, torch::Tensor col_l2,
                    torch::Tensor fmask, torch::Tensor row_w,
-                   int64_t start, int64_t m, int64_t loss_id,
-                   double lr_scale, double momentum, int64_t intercept_row,
-                   double inv_m, torch::Tensor tbits, torch::Tensor mbits,
-                   torch::Tensor col_l1, torch::Tensor cpos,
-                   torch::Tensor cneg) {
+                   int64_t start, int64_t m, int64_t loss_id, double lr_scale,
+                   double momentum, int64_t intercept_row, double inv_m,
+                   torch::Tensor tbits, torch::Tensor mbits,
+                   torch::Tensor col_l1,
+                   torch::Tensor cpos, torch::Tensor cneg) {
     TORCH_CHECK(m >= 1, "m must be >= 1");
-    auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+    auto s = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
                                 col_class, col_fold, col_class2, col_lr,
                                 col_l2, fmask, row_w, m, momentum,
                                 intercept_row, loss_id, 0);
-    TORCH_CHECK(start >= 0 && start % 8 == 0,
-                "start must be a non-negative multiple of 8");
-    TORCH_CHECK(start + (m + 127) / 128 * 128 <= a.n_pad,
-                "start + m_pad must be <= n_pad");
-    auto bits = check_bits(a, tbits, mbits, loss_id);
-    auto l1 = check_l1_opt(col_l1, cpos, cneg, W, momentum);
-    const bool has_V = V.numel() > 0;
-    hipError_t err = skdist_sgd_step_bits(
-        Xs.data_ptr(), XsT.data_ptr(), WbfT.data_ptr(), GT.data_ptr(),
-        W.data_ptr(), has_V ? V.data_ptr() : nullptr, WbfT.data_ptr(),
-        partial.data_ptr(), y.data_ptr(), fold.data_ptr(),
-        col_class.data_ptr(), col_fold.data_ptr(), col_class2.data_ptr(),
-        col_lr.data_ptr(), col_l2.data_ptr(),
-        fmask.numel() ? fmask.data_ptr() : nullptr,
-        row_w.numel() ? row_w.data_ptr() : nullptr, (float)inv_m,
-        start, m, a.n, a.n_pad, a.fa_store, (int)a.fa,
-        (int)a.ncols_pad, (int)a.gt_stride, (int)a.splitk, (int)loss_id,
-        (float)lr_scale, (float)momentum, (int)intercept_row,
-        l1.col_l1, l1.cpos, l1.cneg, bits.tbits, bits.mbits,
-        c10::hip::getCurrentHIPStream().stream());
-    TORCH_CHECK(err == hipSuccess, "skdist_sgd_step_bits: ",
-                hipGetErrorString(err));
+    set_batch(s, start, m, inv_m, lr_scale);
+    check_bits(s, tbits, mbits, loss_id);
+    check_l1_opt(s, col_l1, cpos, cneg, W, momentum);
+    launch_step(s, "skdist_sgd_step_bits");
 }
 
 void sgd_epoch_bits(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                     torch::Tensor W, torch::Tensor V, torch::Tensor WbfT,
-                    torch::Tensor partial, torch::Tensor y,
-                    torch::Tensor fold, torch::Tensor col_class,
-                    torch::Tensor col_fold, torch::Tensor col_class2,
+                    torch::Tensor partial, torch::Tensor y, torch::Tensor fold,
+                    torch::Tensor col_class, torch::Tensor col_fold,
+                    torch::Tensor col_class2,
                     torch::Tensor col_lr, torch::Tensor col_l2,
                     torch::Tensor fmask, torch::Tensor row_w,
-                    torch::Tensor inv_m_cpu, int64_t batch_size,
-                    int64_t loss_id, double lr_scale, double momentum,
-                    int64_t intercept_row, torch::Tensor tbits,
-                    torch::Tensor mbits, torch::Tensor col_l1,
+                    torch::Tensor inv_m_cpu,
+                    int64_t batch_size, int64_t loss_id, double lr_scale,
+                    double momentum, int64_t intercept_row,
+                    torch::Tensor tbits, torch::Tensor mbits,
+                    torch::Tensor col_l1,
                     torch::Tensor cpos, torch::Tensor cneg) {
-    auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+    auto s = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
                                 col_class, col_fold, col_class2, col_lr,
                                 col_l2, fmask, row_w, batch_size, momentum,
                                 intercept_row, loss_id, 0);
-    check_batches(a, batch_size, inv_m_cpu);
-    auto bits = check_bits(a, tbits, mbits, loss_id);
-    auto l1 = check_l1_opt(col_l1, cpos, cneg, W, momentum);
-    enqueue_epoch(a, Xs, XsT, GT, W, V, WbfT, partial, y, fold, col_class,
-                  col_fold, col_class2, col_lr, col_l2, fmask, row_w,
-                  (const float*)inv_m_cpu.data_ptr(), batch_size, loss_id,
-                  (float)lr_scale, momentum, intercept_row, l1, 0,
-                  c10::hip::getCurrentHIPStream().stream(),
-                  "sgd_epoch_bits", bits);
+    check_batches(s, batch_size, inv_m_cpu);
+    check_bits(s, tbits, mbits, loss_id);
+    check_l1_opt(s, col_l1, cpos, cneg, W, momentum);
+    s.lr_scale = (float)lr_scale;
+    enqueue_epoch(s, (const float*)inv_m_cpu.data_ptr(), batch_size,
+                  c10::hip::getCurrentHIPStream().stream(), "sgd_epoch_bits");
 }
 
 void sgd_solve_bits(torch::Tensor Xs, torch::Tensor XsT, torch::Tensor GT,
                     torch::Tensor W, torch::Tensor V, torch::Tensor WbfT,
-                    torch::Tensor partial, torch::Tensor y,
-                    torch::Tensor fold, torch::Tensor col_class,
-                    torch::Tensor col_fold, torch::Tensor col_class2,
+                    torch::Tensor partial, torch::Tensor y, torch::Tensor fold,
+                    torch::Tensor col_class, torch::Tensor col_fold,
+                    torch::Tensor col_class2,
                     torch::Tensor col_lr, torch::Tensor col_l2,
                     torch::Tensor fmask, torch::Tensor row_w,
                     torch::Tensor inv_m_cpu, int64_t batch_size,
                     int64_t loss_id, double momentum, int64_t intercept_row,
-                    int64_t epochs, torch::Tensor tbits,
-                    torch::Tensor mbits, torch::Tensor col_l1,
+                    int64_t epochs,
+                    torch::Tensor tbits, torch::Tensor mbits,
+                    torch::Tensor col_l1,
                     torch::Tensor cpos, torch::Tensor cneg) {
-    auto a = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
+    auto s = check_step_tensors(Xs, XsT, GT, W, V, WbfT, partial, y, fold,
                                 col_class, col_fold, col_class2, col_lr,
                                 col_l2, fmask, row_w, batch_size, momentum,
                                 intercept_row, loss_id, 0);
-    check_batches(a, batch_size, inv_m_cpu);
-    auto bits = check_bits(a, tbits, mbits, loss_id);
-    auto l1 = check_l1_opt(col_l1, cpos, cneg, W, momentum);
-    const float* inv_p = (const float*)inv_m_cpu.data_ptr();
-    auto torch_stream = c10::hip::getCurrentHIPStream().stream();
-    auto body = [&](hipStream_t st) {
-        enqueue_epoch(a, Xs, XsT, GT, W, V, WbfT, partial, y, fold,
-                      col_class, col_fold, col_class2, col_lr, col_l2,
-                      fmask, row_w, inv_p, batch_size, loss_id, 1.0f,
-                      momentum, intercept_row, l1, 0, st,
-                      "sgd_solve_bits", bits);
-    };
-    run_epochs_graphed(epochs, torch_stream, body);
+    check_batches(s, batch_size, inv_m_cpu);
+    check_bits(s, tbits, mbits, loss_id);
+    check_l1_opt(s, col_l1, cpos, cneg, W, momentum);
+    solve_epochs(s, inv_m_cpu, batch_size, epochs, "sgd_solve_bits");
 }
 
 }  // namespace
@@ -1116,20 +984,10 @@ void sp_renorm(torch::Tensor W, torch::Tensor s) {
 
 // ------------------------------------------------------------------ //
 // tree family (tree_kernels.hip, predict_kernels.hip: launchers declared
-// in tree_api.h), scoring, standardize and hashing
+// in tree_api.h), scoring and standardize (sgd_kernels.hip: sgd_api.h)
+// and hashing
 // ------------------------------------------------------------------ //
 
-extern "C" hipError_t skdist_score(
-    const void* Xf, const void* WbfT, const void* yf, void* out,
-    long long m_pad, int fa, int ncols_pad, int mode,
-    hipStream_t stream);
-extern "C" hipError_t skdist_score_groups(
-    const void* Xf, const void* WbfT, const void* yf, void* part,
-    long long m_pad, int fa, int ncols_pad, int gk, int mode,
-    hipStream_t stream);
-extern "C" hipError_t skdist_standardize(
-    const void* X, const void* mean, const void* inv_std, void* out,
-    long long n, int f, int fa, hipStream_t stream);
 extern "C" hipError_t skdist_hash_vectorize(
     const void* bytes, const void* doc_off, long long n_docs, int mode,
     int min_n, int max_n, int n_features, int alt_sign, void* out_keys,

@@ -26,6 +26,7 @@
 //   GT    [ncols_pad][gts]   bf16
 //   partial [SPLITK][fa][ncols_pad] f32
 #include "common.h"
+#include "sgd_api.h"
 
 #include <atomic>
 
@@ -35,6 +36,12 @@
 #define LDC 132  // LDS row stride for the epilogue transpose tile
 // double-buffered LDS tiles carved from the extern-shared base `sm`
 // (one __shared__ object only — guide §5 'Three .s-level traps' (a))
+#define GEMM_LDS 32768
+// dynamic LDS a __launch_bounds__(256, 4) kernel may take: 4 workgroups in
+// a CU's 160 KiB
+#define WG4_LDS_MAX 40960
+#define bufA(b) ((__bf16*)(sm + (b) * 16384))
+#define bufB(b) ((__bf16*)(sm + 8192 + (b) * 16384))
 
 // stage one 128x32 bf16 tile (8 KiB) into linear LDS via 8 glds chunks;
 // each of the 4 waves issues 2. src_row(row) must return the global
@@ -58,6 +65,85 @@ frag_load(const __bf16* lds, int row, int fk) {
     const int phys = (fk >> 3) ^ ((row >> 2) & 3);
     return *(const bf16x8*)(lds + row * BK + phys * 8);
 }
+
+// The 128x128 GEMM main loop of K1 and K5 as an inline body:
+// acc += A[128][fa] * B[128][fa]^T, tiles double-buffered in the first
+// GEMM_LDS bytes of `sm`.  On return the last fragment reads may still be
+// in flight in other waves: the caller puts a barrier before it reuses `sm`.
+static __device__ __forceinline__ void gemm_tile_128(
+    f32x4 (&acc)[4][4], char* sm, const __bf16* Abase, const __bf16* Bbase,
+    int fa, int lane, int w)
+{
+    const int wr = ((w >> 1) & 1) * 64;
+    const int wc = (w & 1) * 64;
+    const int fr = lane & 15;
+    const int fk = (lane >> 4) * 8;
+    const int nk = fa / BK;
+    int cur = 0;
+    STAGE_TILE(bufA(0), Abase + (long long)row * fa);
+    STAGE_TILE(bufB(0), Bbase + (long long)row * fa);
+    for (int kt = 0; kt < nk; ++kt) {
+        __syncthreads();  // staged tile (glds) complete for buf[cur]
+        if (kt + 1 < nk) {
+            STAGE_TILE(bufA(cur ^ 1),
+                       Abase + (long long)row * fa + (kt + 1) * BK);
+            STAGE_TILE(bufB(cur ^ 1),
+                       Bbase + (long long)row * fa + (kt + 1) * BK);
+        }
+        bf16x8 af[4], bfr[4];
+        #pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+            af[mi] = frag_load(bufA(cur), wr + mi * 16 + fr, fk);
+        #pragma unroll
+        for (int ni = 0; ni < 4; ++ni)
+            bfr[ni] = frag_load(bufB(cur), wc + ni * 16 + fr, fk);
+        #pragma unroll
+        for (int mi = 0; mi < 4; ++mi)
+            #pragma unroll
+            for (int ni = 0; ni < 4; ++ni)
+                acc[mi][ni] =
+                    MFMA_BF16_16x16x32(af[mi], bfr[ni], acc[mi][ni]);
+        cur ^= 1;
+    }
+}
+
+// GT tile store of K1: the [BN][LDC] bf16 image in ldsC (column-major, so
+// already transposed) goes out as two 16-byte stores per lane and pass
+static __device__ __forceinline__ void store_gt_tile(
+    const __bf16* ldsC, __bf16* __restrict__ GT, int bn, int bm,
+    int gt_stride, int tid)
+{
+    #pragma unroll
+    for (int i = 0; i < 4; ++i) {
+        const int p = tid + 256 * i;
+        const int col = p >> 3;
+        const int ch = (p & 7) * 16;
+        int4v v0 = *(int4v*)&ldsC[col * LDC + ch];
+        int4v v1 = *(int4v*)&ldsC[col * LDC + ch + 8];
+        __bf16* dst = GT + (long long)(bn + col) * gt_stride + bm + ch;
+        *(int4v*)dst = v0;
+        *(int4v*)(dst + 8) = v1;
+    }
+}
+
+// fp32 z image of the group epilogues (k_fwd_gt_softmax, k_score_groups):
+// 64 rows of the tile at a time, aliasing the GEMM buffers
+#define SMX_ZLD 129                    // fp32 row stride of the z image
+#define SMX_ZBYTES (64 * SMX_ZLD * 4)  // 33024, covers the 32 KiB of bufs
+static_assert(SMX_ZBYTES >= GEMM_LDS, "the z image covers the GEMM buffers");
+
+// a wave writes its 64x64 of acc to rows 0..63 of zS; called by the two
+// waves that hold rows 64h .. 64h+63 of the tile.  A macro like STAGE_TILE:
+// as an inline function it lets the compiler merge the first spill of
+// k_score_groups' two epilogue instantiations, which is another kernel
+#define SPILL_Z_HALF(acc, zS, wc, fr, rw)                                   \
+    do {                                                                    \
+        _Pragma("unroll") for (int mi = 0; mi < 4; ++mi)                    \
+            _Pragma("unroll") for (int ni = 0; ni < 4; ++ni)                \
+                _Pragma("unroll") for (int r = 0; r < 4; ++r)               \
+                    (zS)[(mi * 16 + (rw) * 4 + r) * SMX_ZLD + (wc) +        \
+                         ni * 16 + (fr)] = (acc)[mi][ni][r];                \
+    } while (0)
 
 // ---------------------------------------------------------------------- //
 // K1: fused forward GEMM + loss gradient + transposed store
@@ -125,6 +211,9 @@ static __device__ __forceinline__ void fwd_epilogue(
     }
 }
 
+#define FWD_LDS (BN * LDC * 2 + 7 * 512 + 16)  // tile, 7 arrays, gen_s
+static_assert(FWD_LDS <= WG4_LDS_MAX, "k_fwd_gt: 4 workgroups per CU");
+
 extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt(
     const __bf16* __restrict__ Xs,    // [n_pad][fa]
     const __bf16* __restrict__ WbfT,  // [ncols_pad][fa]
@@ -139,8 +228,6 @@ extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt(
     int loss_id)
 {
     extern __shared__ __attribute__((aligned(16))) char sm[];
-    #define bufA(b) ((__bf16*)(sm + (b) * 16384))
-    #define bufB(b) ((__bf16*)(sm + 8192 + (b) * 16384))
     __bf16* ldsC = (__bf16*)sm;             // [BN][LDC], aliases the bufs
     char* meta = sm + BN * LDC * 2;
     float* y_s = (float*)meta;              // [BM]
@@ -151,6 +238,7 @@ extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt(
     float* rw_s = (float*)(meta + 2560);    // [BM]
     int* ok_s = (int*)(meta + 3072);        // [BM] row may train (< m)
     int* gen_s = (int*)(meta + 3584);       // [2] a wave saw a class column
+    static_assert(BN * LDC * 2 + 3584 + 8 <= FWD_LDS, "carve-up");
 
     const int tid = threadIdx.x;
     const int bm = blockIdx.x * BM;
@@ -182,36 +270,9 @@ extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt(
     const int wr = ((w >> 1) & 1) * 64;
     const int wc = (w & 1) * 64;
     const int fr = lane & 15;
-    const int fk = (lane >> 4) * 8;
 
     f32x4 acc[4][4] = {};
-    const int nk = fa / BK;
-    int cur = 0;
-    STAGE_TILE(bufA(0), Abase + (long long)row * fa);
-    STAGE_TILE(bufB(0), Bbase + (long long)row * fa);
-    for (int kt = 0; kt < nk; ++kt) {
-        __syncthreads();  // staged tile (glds) complete for buf[cur]
-        if (kt + 1 < nk) {
-            STAGE_TILE(bufA(cur ^ 1),
-                       Abase + (long long)row * fa + (kt + 1) * BK);
-            STAGE_TILE(bufB(cur ^ 1),
-                       Bbase + (long long)row * fa + (kt + 1) * BK);
-        }
-        bf16x8 af[4], bfr[4];
-        #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-            af[mi] = frag_load(bufA(cur), wr + mi * 16 + fr, fk);
-        #pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-            bfr[ni] = frag_load(bufB(cur), wc + ni * 16 + fr, fk);
-        #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-            #pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-                acc[mi][ni] =
-                    MFMA_BF16_16x16x32(af[mi], bfr[ni], acc[mi][ni]);
-        cur ^= 1;
-    }
+    gemm_tile_128(acc, sm, Abase, Bbase, fa, lane, w);
 
     // epilogue: z -> masked dloss -> bf16, transposed through LDS.  The
     // barrier also orders the prologue's metadata writes (nk >= 1 put
@@ -238,17 +299,7 @@ extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt(
     }
     #undef FWD_EPILOGUE
     __syncthreads();
-    #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int p = tid + 256 * i;
-        const int col = p >> 3;
-        const int ch = (p & 7) * 16;
-        int4v v0 = *(int4v*)&ldsC[col * LDC + ch];
-        int4v v1 = *(int4v*)&ldsC[col * LDC + ch + 8];
-        __bf16* dst = GT + (long long)(bn + col) * gt_stride + bm + ch;
-        *(int4v*)dst = v0;
-        *(int4v*)(dst + 8) = v1;
-    }
+    store_gt_tile(ldsC, GT, bn, bm, gt_stride, tid);
 }
 
 // ---------------------------------------------------------------------- //
@@ -283,6 +334,7 @@ extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt(
 // __launch_bounds__(256, 4): 128 VGPRs, no AGPRs, no scratch (k_fwd_gt: 121).
 // ---------------------------------------------------------------------- //
 #define BITS_LDS (BN * LDC * 2 + 4 * 512 + 2 * 2048)
+static_assert(BITS_LDS <= WG4_LDS_MAX, "k_fwd_gt_bits: 4 workgroups per CU");
 
 template <int LOSS, bool HASM>
 static __device__ __forceinline__ void fwd_epilogue_bits(
@@ -348,6 +400,7 @@ extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt_bits(
     int* ok_s = (int*)(meta + 1536);        // [BM] row may train (< m)
     int* tb_s = (int*)(meta + 2048);        // [4][BM] target words
     int* mb_s = (int*)(meta + 4096);        // [4][BM] mask words
+    static_assert(BN * LDC * 2 + 4096 + 2048 <= BITS_LDS, "carve-up");
 
     const int tid = threadIdx.x;
     const int bm = blockIdx.x * BM;
@@ -384,37 +437,9 @@ extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt_bits(
     const int wr = ((w >> 1) & 1) * 64;
     const int wc = (w & 1) * 64;
     const int fr = lane & 15;
-    const int fk = (lane >> 4) * 8;
 
-    // the GEMM main loop of k_fwd_gt
     f32x4 acc[4][4] = {};
-    const int nk = fa / BK;
-    int cur = 0;
-    STAGE_TILE(bufA(0), Abase + (long long)row * fa);
-    STAGE_TILE(bufB(0), Bbase + (long long)row * fa);
-    for (int kt = 0; kt < nk; ++kt) {
-        __syncthreads();  // staged tile (glds) complete for buf[cur]
-        if (kt + 1 < nk) {
-            STAGE_TILE(bufA(cur ^ 1),
-                       Abase + (long long)row * fa + (kt + 1) * BK);
-            STAGE_TILE(bufB(cur ^ 1),
-                       Bbase + (long long)row * fa + (kt + 1) * BK);
-        }
-        bf16x8 af[4], bfr[4];
-        #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-            af[mi] = frag_load(bufA(cur), wr + mi * 16 + fr, fk);
-        #pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-            bfr[ni] = frag_load(bufB(cur), wc + ni * 16 + fr, fk);
-        #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-            #pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-                acc[mi][ni] =
-                    MFMA_BF16_16x16x32(af[mi], bfr[ni], acc[mi][ni]);
-        cur ^= 1;
-    }
+    gemm_tile_128(acc, sm, Abase, Bbase, fa, lane, w);
 
     // epilogue, as k_fwd_gt: the barrier ends the reads of the GEMM buffers
     // and orders the prologue's metadata writes before the reads below
@@ -438,17 +463,7 @@ extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt_bits(
     }
     #undef FWD_EPILOGUE_BITS
     __syncthreads();
-    #pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const int p = tid + 256 * i;
-        const int col = p >> 3;
-        const int ch = (p & 7) * 16;
-        int4v v0 = *(int4v*)&ldsC[col * LDC + ch];
-        int4v v1 = *(int4v*)&ldsC[col * LDC + ch + 8];
-        __bf16* dst = GT + (long long)(bn + col) * gt_stride + bm + ch;
-        *(int4v*)dst = v0;
-        *(int4v*)(dst + 8) = v1;
-    }
+    store_gt_tile(ldsC, GT, bn, bm, gt_stride, tid);
 }
 
 // ---------------------------------------------------------------------- //
@@ -481,9 +496,9 @@ extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt_bits(
 // __launch_bounds__(256, 4): 115 VGPRs, no AGPRs, no scratch, 36096 B of
 // LDS: 4 workgroups per CU (4 waves per SIMD), as k_fwd_gt.
 // ---------------------------------------------------------------------- //
-#define SMX_ZLD 129                    // fp32 row stride of the z image
-#define SMX_ZBYTES (64 * SMX_ZLD * 4)  // 33024, covers the 32 KiB of bufs
 #define SMX_LDS (SMX_ZBYTES + 6 * 512)
+static_assert(SMX_LDS <= WG4_LDS_MAX,
+              "k_fwd_gt_softmax: 4 workgroups per CU");
 
 extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt_softmax(
     const __bf16* __restrict__ Xs,    // [n_pad][fa]
@@ -507,6 +522,7 @@ extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt_softmax(
     int* cfold_s = (int*)(meta + 1536);     // [BN]
     float* rw_s = (float*)(meta + 2048);    // [BM]
     int* ok_s = (int*)(meta + 2560);        // [BM] row may train
+    static_assert(SMX_ZBYTES + 2560 + 512 <= SMX_LDS, "carve-up");
 
     const int tid = threadIdx.x;
     const int bm = blockIdx.x * BM;
@@ -533,37 +549,9 @@ extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt_softmax(
     const int wr = ((w >> 1) & 1) * 64;
     const int wc = (w & 1) * 64;
     const int fr = lane & 15;
-    const int fk = (lane >> 4) * 8;
 
-    // the GEMM main loop of k_fwd_gt
     f32x4 acc[4][4] = {};
-    const int nk = fa / BK;
-    int cur = 0;
-    STAGE_TILE(bufA(0), Abase + (long long)row * fa);
-    STAGE_TILE(bufB(0), Bbase + (long long)row * fa);
-    for (int kt = 0; kt < nk; ++kt) {
-        __syncthreads();  // staged tile (glds) complete for buf[cur]
-        if (kt + 1 < nk) {
-            STAGE_TILE(bufA(cur ^ 1),
-                       Abase + (long long)row * fa + (kt + 1) * BK);
-            STAGE_TILE(bufB(cur ^ 1),
-                       Bbase + (long long)row * fa + (kt + 1) * BK);
-        }
-        bf16x8 af[4], bfr[4];
-        #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-            af[mi] = frag_load(bufA(cur), wr + mi * 16 + fr, fk);
-        #pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-            bfr[ni] = frag_load(bufB(cur), wc + ni * 16 + fr, fk);
-        #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-            #pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-                acc[mi][ni] =
-                    MFMA_BF16_16x16x32(af[mi], bfr[ni], acc[mi][ni]);
-        cur ^= 1;
-    }
+    gemm_tile_128(acc, sm, Abase, Bbase, fa, lane, w);
 
     // every wave is done reading the GEMM buffers, and the prologue's
     // metadata is visible
@@ -572,16 +560,7 @@ extern "C" __global__ __launch_bounds__(256, 4) void k_fwd_gt_softmax(
     const int gpt = BN / gk;
     const int ncl = gpt * gk;   // live columns of the tile
     for (int h = 0; h < 2; ++h) {
-        if (wr == h * 64) {     // the two waves holding rows 64h .. 64h+63
-            #pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-                #pragma unroll
-                for (int ni = 0; ni < 4; ++ni)
-                    #pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        zS[(mi * 16 + rw * 4 + r) * SMX_ZLD + wc + ni * 16 +
-                           fr] = acc[mi][ni][r];
-        }
+        if (wr == h * 64) SPILL_Z_HALF(acc, zS, wc, fr, rw);
         __syncthreads();
         {
             const int R = h * 64 + lane;  // this lane's row of the tile
@@ -1129,170 +1108,85 @@ extern "C" __global__ __launch_bounds__(128) void k_reduce_update_l1(
 }
 
 // ---------------------------------------------------------------------- //
-// host launcher.  col_l1 == null is the L2-only step (k_reduce_update);
-// otherwise cpos/cneg are the [fa][ncols_pad] L1 credit tables and K3 is
-// k_reduce_update_l1.  K1 and K2 are shared.  loss_id == LOSS_SOFTMAX
-// launches k_fwd_gt_softmax with group width group_k (2..128) as K1; every
-// other loss launches k_fwd_gt and takes group_k == 0.  Tbits != null
-// launches k_fwd_gt_bits as K1 (not with the softmax loss), with Mbits the
-// optional mask plane; null Tbits launches the kernels above, unchanged.
+// host launcher of one step (SgdStep: sgd_api.h).  K1 is k_fwd_gt_bits with
+// Tbits, k_fwd_gt_softmax with LOSS_SOFTMAX, else k_fwd_gt; K2 is shared;
+// K3 is k_reduce_update_l1 with col_l1, else k_reduce_update.
 // ---------------------------------------------------------------------- //
-static hipError_t sgd_step_impl(
-    const void* Xs, const void* XsT, const void* WbfT_in,
-    void* GT, void* W, void* V, void* WbfT, void* partial,
-    const void* y, const void* fold,
-    const void* col_class, const void* col_fold, const void* col_class2,
-    const void* col_lr, const void* col_l2, const void* fmask,
-    const void* row_w, float inv_m,
-    long long start, long long m, long long n, long long n_pad,
-    long long fa_store, int fa, int ncols_pad,
-    int gt_stride, int splitk, int loss_id,
-    float lr_scale, float momentum, int intercept_row,
-    const void* col_l1, void* cpos, void* cneg, int group_k,
-    const void* Tbits, const void* Mbits, hipStream_t stream)
+hipError_t skdist_sgd_step(const SgdStep& s, hipStream_t stream)
 {
-    const int m_pad = (int)((m + BM - 1) / BM) * BM;
+    const bool softmax = s.loss_id == LOSS_SOFTMAX;
+    if (softmax) {
+        if (s.group_k < 2 || s.group_k > BN || s.Tbits != nullptr)
+            return hipErrorInvalidValue;
+    } else if (s.group_k != 0) {
+        return hipErrorInvalidValue;
+    }
+    if (s.Mbits != nullptr && s.Tbits == nullptr)
+        return hipErrorInvalidValue;  // a mask plane needs targets
+    const int n_l1 = (s.col_l1 != nullptr) + (s.cpos != nullptr) +
+                     (s.cneg != nullptr);
+    if (n_l1 != 0 && n_l1 != 3) return hipErrorInvalidValue;
+
+    const int m_pad = (int)((s.m + BM - 1) / BM) * BM;
     {
-        dim3 grid(m_pad / BM, ncols_pad / BN);
-        size_t lds = (size_t)BN * LDC * 2 + 3600;
-        if (Tbits != nullptr) {
-            if (loss_id == LOSS_SOFTMAX || group_k != 0)
-                return hipErrorInvalidValue;
+        dim3 grid(m_pad / BM, s.ncols_pad / BN);
+        if (s.Tbits != nullptr) {
             hipLaunchKernelGGL(k_fwd_gt_bits, grid, dim3(256), BITS_LDS,
                                stream,
-                               (const __bf16*)Xs, (const __bf16*)WbfT_in,
-                               (__bf16*)GT, (const int*)fold,
-                               (const int*)col_fold, (const float*)row_w,
-                               (const int*)Tbits, (const int*)Mbits,
-                               (int)start, (int)m, n, fa, ncols_pad,
-                               gt_stride, loss_id);
-        } else if (Mbits != nullptr) {
-            return hipErrorInvalidValue;  // a mask plane needs targets
-        } else if (loss_id == LOSS_SOFTMAX) {
-            if (group_k < 2 || group_k > BN) return hipErrorInvalidValue;
-            hipLaunchKernelGGL(k_fwd_gt_softmax, grid, dim3(256), SMX_LDS,
-                               stream,
-                               (const __bf16*)Xs, (const __bf16*)WbfT_in,
-                               (__bf16*)GT, (const float*)y,
-                               (const int*)fold, (const int*)col_class,
-                               (const int*)col_fold, (const int*)col_class2,
-                               (const float*)row_w, (int)start, (int)m, n,
-                               fa, ncols_pad, gt_stride, group_k);
+                               (const __bf16*)s.Xs, (const __bf16*)s.WbfT,
+                               (__bf16*)s.GT, (const int*)s.fold,
+                               (const int*)s.col_fold, (const float*)s.row_w,
+                               (const int*)s.Tbits, (const int*)s.Mbits,
+                               (int)s.start, (int)s.m, s.n, s.fa,
+                               s.ncols_pad, s.gt_stride, s.loss_id);
         } else {
-            if (group_k != 0) return hipErrorInvalidValue;
-            hipLaunchKernelGGL(k_fwd_gt, grid, dim3(256), lds, stream,
-                               (const __bf16*)Xs, (const __bf16*)WbfT_in,
-                               (__bf16*)GT, (const float*)y,
-                               (const int*)fold, (const int*)col_class,
-                               (const int*)col_fold, (const int*)col_class2,
-                               (const float*)row_w, (int)start, (int)m, n,
-                               fa, ncols_pad, gt_stride, loss_id);
+            // the two kernels take the same arguments; the last one is the
+            // group width for the softmax loss, the loss otherwise
+            hipLaunchKernelGGL(softmax ? k_fwd_gt_softmax : k_fwd_gt, grid,
+                               dim3(256), softmax ? SMX_LDS : FWD_LDS,
+                               stream,
+                               (const __bf16*)s.Xs, (const __bf16*)s.WbfT,
+                               (__bf16*)s.GT, (const float*)s.y,
+                               (const int*)s.fold, (const int*)s.col_class,
+                               (const int*)s.col_fold,
+                               (const int*)s.col_class2,
+                               (const float*)s.row_w, (int)s.start,
+                               (int)s.m, s.n, s.fa, s.ncols_pad,
+                               s.gt_stride, softmax ? s.group_k : s.loss_id);
         }
         HIP_CHECK(hipGetLastError());
     }
-    HIP_CHECK(launch_grad_partial(XsT, GT, partial, (int)start, m_pad, n_pad,
-                                  fa_store, fa, ncols_pad, gt_stride, splitk,
-                                  0, stream));
+    HIP_CHECK(launch_grad_partial(s.XsT, s.GT, s.partial, (int)s.start,
+                                  m_pad, s.n_pad, s.fa_store, s.fa,
+                                  s.ncols_pad, s.gt_stride, s.splitk, 0,
+                                  stream));
     {
-        dim3 grid(ncols_pad / 128, fa);
-        if (col_l1 == nullptr) {
+        dim3 grid(s.ncols_pad / 128, s.fa);
+        if (s.col_l1 == nullptr) {
             hipLaunchKernelGGL(k_reduce_update, grid, dim3(128), 0, stream,
-                               (const float*)partial, (float*)W, (float*)V,
-                               (__bf16*)WbfT, (const float*)col_lr,
-                               (const float*)col_l2,
-                               (const unsigned char*)fmask, inv_m,
-                               lr_scale, momentum, intercept_row, splitk,
-                               fa, ncols_pad);
+                               (const float*)s.partial, (float*)s.W,
+                               (float*)s.V, (__bf16*)s.WbfT,
+                               (const float*)s.col_lr,
+                               (const float*)s.col_l2,
+                               (const unsigned char*)s.fmask, s.inv_m,
+                               s.lr_scale, s.momentum, s.intercept_row,
+                               s.splitk, s.fa, s.ncols_pad);
         } else {
             hipLaunchKernelGGL(k_reduce_update_l1, grid, dim3(128), 0,
                                stream,
-                               (const float*)partial, (float*)W, (float*)V,
-                               (__bf16*)WbfT, (const float*)col_lr,
-                               (const float*)col_l2,
-                               (const unsigned char*)fmask, inv_m,
-                               lr_scale, momentum, intercept_row, splitk,
-                               fa, ncols_pad, (const float*)col_l1,
-                               (float*)cpos, (float*)cneg,
-                               1.f / (1.f - momentum));
+                               (const float*)s.partial, (float*)s.W,
+                               (float*)s.V, (__bf16*)s.WbfT,
+                               (const float*)s.col_lr,
+                               (const float*)s.col_l2,
+                               (const unsigned char*)s.fmask, s.inv_m,
+                               s.lr_scale, s.momentum, s.intercept_row,
+                               s.splitk, s.fa, s.ncols_pad,
+                               (const float*)s.col_l1, (float*)s.cpos,
+                               (float*)s.cneg, 1.f / (1.f - s.momentum));
         }
         HIP_CHECK(hipGetLastError());
     }
     return hipSuccess;
-}
-
-extern "C" hipError_t skdist_sgd_step(
-    const void* Xs, const void* XsT, const void* WbfT_in,
-    void* GT, void* W, void* V, void* WbfT, void* partial,
-    const void* y, const void* fold,
-    const void* col_class, const void* col_fold, const void* col_class2,
-    const void* col_lr, const void* col_l2, const void* fmask,
-    const void* row_w, float inv_m,
-    long long start, long long m, long long n, long long n_pad,
-    long long fa_store, int fa, int ncols_pad,
-    int gt_stride, int splitk, int loss_id,
-    float lr_scale, float momentum, int intercept_row, int group_k,
-    hipStream_t stream)
-{
-    return sgd_step_impl(Xs, XsT, WbfT_in, GT, W, V, WbfT, partial, y,
-                         fold, col_class, col_fold, col_class2, col_lr,
-                         col_l2, fmask, row_w, inv_m, start, m, n, n_pad,
-                         fa_store, fa, ncols_pad, gt_stride, splitk,
-                         loss_id, lr_scale, momentum, intercept_row,
-                         nullptr, nullptr, nullptr, group_k, nullptr,
-                         nullptr, stream);
-}
-
-extern "C" hipError_t skdist_sgd_step_l1(
-    const void* Xs, const void* XsT, const void* WbfT_in,
-    void* GT, void* W, void* V, void* WbfT, void* partial,
-    const void* y, const void* fold,
-    const void* col_class, const void* col_fold, const void* col_class2,
-    const void* col_lr, const void* col_l2, const void* fmask,
-    const void* row_w, float inv_m,
-    long long start, long long m, long long n, long long n_pad,
-    long long fa_store, int fa, int ncols_pad,
-    int gt_stride, int splitk, int loss_id,
-    float lr_scale, float momentum, int intercept_row,
-    const void* col_l1, void* cpos, void* cneg, int group_k,
-    hipStream_t stream)
-{
-    if (col_l1 == nullptr || cpos == nullptr || cneg == nullptr)
-        return hipErrorInvalidValue;
-    return sgd_step_impl(Xs, XsT, WbfT_in, GT, W, V, WbfT, partial, y,
-                         fold, col_class, col_fold, col_class2, col_lr,
-                         col_l2, fmask, row_w, inv_m, start, m, n, n_pad,
-                         fa_store, fa, ncols_pad, gt_stride, splitk,
-                         loss_id, lr_scale, momentum, intercept_row,
-                         col_l1, cpos, cneg, group_k, nullptr, nullptr,
-                         stream);
-}
-
-// the step with per-element targets (k_fwd_gt_bits as K1).  col_l1 == null
-// is the L2-only update, otherwise cpos / cneg are the L1 credit tables;
-// Mbits == null trains every element the fold and row tests let through.
-extern "C" hipError_t skdist_sgd_step_bits(
-    const void* Xs, const void* XsT, const void* WbfT_in,
-    void* GT, void* W, void* V, void* WbfT, void* partial,
-    const void* y, const void* fold,
-    const void* col_class, const void* col_fold, const void* col_class2,
-    const void* col_lr, const void* col_l2, const void* fmask,
-    const void* row_w, float inv_m,
-    long long start, long long m, long long n, long long n_pad,
-    long long fa_store, int fa, int ncols_pad,
-    int gt_stride, int splitk, int loss_id,
-    float lr_scale, float momentum, int intercept_row,
-    const void* col_l1, void* cpos, void* cneg,
-    const void* Tbits, const void* Mbits, hipStream_t stream)
-{
-    if (Tbits == nullptr) return hipErrorInvalidValue;
-    if (col_l1 != nullptr && (cpos == nullptr || cneg == nullptr))
-        return hipErrorInvalidValue;
-    return sgd_step_impl(Xs, XsT, WbfT_in, GT, W, V, WbfT, partial, y,
-                         fold, col_class, col_fold, col_class2, col_lr,
-                         col_l2, fmask, row_w, inv_m, start, m, n, n_pad,
-                         fa_store, fa, ncols_pad, gt_stride, splitk,
-                         loss_id, lr_scale, momentum, intercept_row,
-                         col_l1, cpos, cneg, 0, Tbits, Mbits, stream);
 }
 
 // ---------------------------------------------------------------------- //
@@ -1360,46 +1254,7 @@ extern "C" hipError_t skdist_standardize(
 // grid: (m_pad/128, ncols_pad/128), block 256 (4 waves of 64x64).
 // ---------------------------------------------------------------------- //
 
-// The GEMM main loop of k_fwd_gt as an inline body for the scoring kernels:
-// acc += A[128][fa] * B[128][fa]^T, tiles double-buffered in the first
-// 32 KiB of `sm`.  On return the last fragment reads may still be in
-// flight in other waves: the caller puts a barrier before it reuses `sm`.
-static __device__ __forceinline__ void score_gemm_tile(
-    f32x4 (&acc)[4][4], char* sm, const __bf16* Abase, const __bf16* Bbase,
-    int fa, int lane, int w)
-{
-    const int wr = ((w >> 1) & 1) * 64;
-    const int wc = (w & 1) * 64;
-    const int fr = lane & 15;
-    const int fk = (lane >> 4) * 8;
-    const int nk = fa / BK;
-    int cur = 0;
-    STAGE_TILE(bufA(0), Abase + (long long)row * fa);
-    STAGE_TILE(bufB(0), Bbase + (long long)row * fa);
-    for (int kt = 0; kt < nk; ++kt) {
-        __syncthreads();  // staged tile (glds) complete for buf[cur]
-        if (kt + 1 < nk) {
-            STAGE_TILE(bufA(cur ^ 1),
-                       Abase + (long long)row * fa + (kt + 1) * BK);
-            STAGE_TILE(bufB(cur ^ 1),
-                       Bbase + (long long)row * fa + (kt + 1) * BK);
-        }
-        bf16x8 af[4], bfr[4];
-        #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-            af[mi] = frag_load(bufA(cur), wr + mi * 16 + fr, fk);
-        #pragma unroll
-        for (int ni = 0; ni < 4; ++ni)
-            bfr[ni] = frag_load(bufB(cur), wc + ni * 16 + fr, fk);
-        #pragma unroll
-        for (int mi = 0; mi < 4; ++mi)
-            #pragma unroll
-            for (int ni = 0; ni < 4; ++ni)
-                acc[mi][ni] =
-                    MFMA_BF16_16x16x32(af[mi], bfr[ni], acc[mi][ni]);
-        cur ^= 1;
-    }
-}
+#define SCORE_LDS (GEMM_LDS + 512 + 132 * 4)  // bufs, y_s, red
 
 extern "C" __global__ __launch_bounds__(256) void k_score(
     const __bf16* __restrict__ Xf,    // [m_pad][fa] gathered fold rows
@@ -1409,8 +1264,8 @@ extern "C" __global__ __launch_bounds__(256) void k_score(
     int fa, int ncols_pad, int mode)
 {
     extern __shared__ __attribute__((aligned(16))) char sm[];
-    float* y_s = (float*)(sm + 32768);        // [128]
-    float* red = (float*)(sm + 33280);        // [132] per-col partials
+    float* y_s = (float*)(sm + GEMM_LDS);          // [128]
+    float* red = (float*)(sm + GEMM_LDS + 512);    // [132] per-col partials
 
     const int tid = threadIdx.x;
     const int bm = blockIdx.x * 128;
@@ -1426,7 +1281,7 @@ extern "C" __global__ __launch_bounds__(256) void k_score(
     const int fr = lane & 15;
 
     f32x4 acc[4][4] = {};
-    score_gemm_tile(acc, sm, Abase, Bbase, fa, lane, w);
+    gemm_tile_128(acc, sm, Abase, Bbase, fa, lane, w);
     __syncthreads();
 
     // per-lane partials over this wave's 16 rows x 4 col-groups
@@ -1476,7 +1331,7 @@ extern "C" hipError_t skdist_score(
     hipStream_t stream)
 {
     dim3 grid((unsigned)(m_pad / 128), ncols_pad / 128);
-    hipLaunchKernelGGL(k_score, grid, dim3(256), 33280 + 132 * 4, stream,
+    hipLaunchKernelGGL(k_score, grid, dim3(256), SCORE_LDS, stream,
                        (const __bf16*)Xf, (const __bf16*)WbfT,
                        (const float*)yf, (float*)out, fa, ncols_pad,
                        mode);
@@ -1521,6 +1376,7 @@ extern "C" hipError_t skdist_score(
 // ---------------------------------------------------------------------- //
 #define NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))
 #define SCG_LDS (SMX_ZBYTES + 512)
+static_assert(SCG_LDS <= WG4_LDS_MAX, "k_score_groups: 4 workgroups per CU");
 
 template <int MODE>
 static __device__ __forceinline__ void score_groups_epilogue(
@@ -1534,16 +1390,7 @@ static __device__ __forceinline__ void score_groups_epilogue(
     const int gpt = BN / gk;
     float carry = 0.f;  // lane i: total of group w + 4 * i over both halves
     for (int h = 0; h < 2; ++h) {
-        if (wr == h * 64) {     // the two waves holding rows 64h .. 64h+63
-            #pragma unroll
-            for (int mi = 0; mi < 4; ++mi)
-                #pragma unroll
-                for (int ni = 0; ni < 4; ++ni)
-                    #pragma unroll
-                    for (int r = 0; r < 4; ++r)
-                        zS[(mi * 16 + rw * 4 + r) * SMX_ZLD + wc + ni * 16 +
-                           fr] = acc[mi][ni][r];
-        }
+        if (wr == h * 64) SPILL_Z_HALF(acc, zS, wc, fr, rw);
         __syncthreads();
         const float yv = y_s[h * 64 + lane];
         const bool valid = !(yv < -1e29f);
@@ -1598,7 +1445,7 @@ void k_score_groups(
     if (tid < BM) y_s[tid] = yf[bm + tid];
 
     f32x4 acc[4][4] = {};
-    score_gemm_tile(acc, sm, Xf + (long long)bm * fa,
+    gemm_tile_128(acc, sm, Xf + (long long)bm * fa,
                     WbfT + (long long)bn * fa, fa, lane, w);
     // every wave is done reading the GEMM buffers, and y_s is visible
     __syncthreads();

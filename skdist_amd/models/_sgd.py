@@ -690,6 +690,14 @@ def batched_scores_by_fold(ds, W, model_folds, col_class, n_classes,
         and metric in group_modes
         and 3 <= n_classes <= 128
     )
+    # F1 of a 2..128-class search: per-class predicted and true-positive
+    # counts in the GEMM epilogue (k_score_counts)
+    use_hip_counts = (
+        _use_hip(device)
+        and metric in _F1_METRICS
+        and ds.classes_ is not None
+        and 2 <= n_classes <= 128
+    )
     for f in np.unique(model_folds[model_folds >= 0]):
         mids = np.flatnonzero(model_folds == f)
         cols_np = (mids[:, None] * cpm + np.arange(cpm)).ravel()
@@ -704,6 +712,10 @@ def batched_scores_by_fold(ds, W, model_folds, col_class, n_classes,
         if use_hip_groups:
             out[mids] = _score_fold_hip_groups(
                 ds, Wf, rows, n_classes, group_modes[metric])
+            continue
+        if use_hip_counts:
+            out[mids] = _score_fold_hip_counts(
+                ds, Wf, rows, n_classes, metric)
             continue
         spec = _Shim()
         spec.col_class = torch.as_tensor(
@@ -788,6 +800,65 @@ def _score_fold_hip_groups(ds, Wf, rows, gk, mode):
     require_hip().score_fold_groups(Xb, WbfT, yf, part, gk, mode)
     tot = part.to(torch.float64).sum(dim=0)[:nm].cpu().numpy()
     return (tot if mode == 0 else -tot) / max(m, 1)
+
+
+_F1_METRICS = ("f1", "f1_weighted", "f1_macro")
+
+
+def _f1_from_counts(tp, pred_ct, support, metric):
+    """F1 of ``metric`` from float64 tensors [n_models, k]: true positives,
+    predicted and true counts per class.  A class nobody predicted, or
+    with no rows, scores 0 (the 1e-12 clamps).  Returns np.ndarray
+    [n_models]."""
+    prec = tp / pred_ct.clamp_min(1e-12)
+    rec = tp / support.clamp_min(1e-12)
+    f1 = 2 * prec * rec / (prec + rec).clamp_min(1e-12)
+    if metric == "f1":
+        return f1[:, 1].cpu().numpy()
+    if metric == "f1_macro":
+        return f1.mean(dim=1).cpu().numpy()
+    w = support / support.sum(dim=1, keepdim=True).clamp_min(1)
+    return (f1 * w).sum(dim=1).cpu().numpy()
+
+
+def _score_fold_hip_counts(ds, Wf, rows, n_classes, metric):
+    """One fold of an F1-scored search through k_score_counts
+    (sgd_kernels.hip).  ``Wf`` [fa, n_models * gk] as for
+    ``_score_fold_hip_groups``, with gk = 1 for a binary search (one
+    column per model, the identity layout).  The kernel leaves, per
+    column, the rows predicted as its class and those of them that are
+    right; the support is the fold's own class histogram, and the binary
+    class 0 follows from class 1.  Returns one F1 per model: the argmax is
+    taken of the fp32 accumulator, never rounded to bf16."""
+    from ..ops import require_hip, softmax_columns
+
+    device = ds.device
+    m = len(rows)
+    fa = ds.Xaug.shape[1]
+    k = max(n_classes, 2)
+    gk = k if k > 2 else 1
+    nm = Wf.shape[1] // gk
+    cols, ncp = softmax_columns(nm, gk)
+    cols = torch.as_tensor(cols, device=device)
+    m_pad = max(128, (m + 127) // 128 * 128)
+    Xb = torch.zeros(m_pad, fa, dtype=ds.comp_dtype, device=device)
+    torch.index_select(ds.Xaug, 0, rows, out=Xb[:m])
+    yf = torch.full((m_pad,), -1e30, dtype=torch.float32, device=device)
+    yf[:m] = ds.y_float.index_select(0, rows)
+    WbfT = torch.zeros(ncp, fa, dtype=ds.comp_dtype, device=device)
+    WbfT[cols] = Wf.t()
+    cnt = torch.zeros(2, ncp, dtype=torch.int32, device=device)
+    require_hip().score_fold_counts(Xb, WbfT, yf, cnt, gk)
+    pc, tp = cnt[:, cols].to(torch.float64).view(2, nm, gk)
+    # the kernel's own reading of y: clamped into the classes
+    yi = yf[:m].to(torch.int64).clamp_(0, k - 1)
+    support = torch.bincount(yi, minlength=k).to(torch.float64)
+    if gk == 1:
+        # class 0 is everything class 1 is not
+        pc1, tp1 = pc, tp
+        pc = torch.cat([m - pc1, pc1], dim=1)
+        tp = torch.cat([(m - support[1]) - (pc1 - tp1), tp1], dim=1)
+    return _f1_from_counts(tp, pc, support.expand(nm, k), metric)
 
 
 class _MetricState:
@@ -896,15 +967,7 @@ class _MetricState:
             tp = conf.diagonal(dim1=1, dim2=2)              # [nm, k]
             support = conf.sum(dim=2)                       # true counts
             pred_ct = conf.sum(dim=1)
-            prec = tp / pred_ct.clamp_min(1e-12)
-            rec = tp / support.clamp_min(1e-12)
-            f1 = 2 * prec * rec / (prec + rec).clamp_min(1e-12)
-            if self.metric == "f1":
-                return f1[:, 1].cpu().numpy()
-            if self.metric == "f1_macro":
-                return f1.mean(dim=1).cpu().numpy()
-            w = support / support.sum(dim=1, keepdim=True).clamp_min(1)
-            return (f1 * w).sum(dim=1).cpu().numpy()
+            return _f1_from_counts(tp, pred_ct, support, self.metric)
         if self.metric == "neg_log_loss":
             return (-(self.loss_sum / self.count.clamp_min(1))).cpu().numpy()
         if self.metric == "roc_auc":

@@ -1416,6 +1416,37 @@ void score_fold_groups(torch::Tensor Xf, torch::Tensor WbfT,
                 hipGetErrorString(err));
 }
 
+// F1 fold scoring: the operands of score_fold_groups, gk == 1 for a binary
+// search (one column per model).  cnt [2, ncols_pad] int32, zeroed by the
+// caller: per column the rows predicted as its class, and those of them
+// whose y is that class; the kernel adds into it
+void score_fold_counts(torch::Tensor Xf, torch::Tensor WbfT,
+                       torch::Tensor yf, torch::Tensor cnt, int64_t gk) {
+    TORCH_CHECK(gk == 1 || (gk >= 3 && gk <= 128),
+                "gk must be 1 or in 3..128");
+    check_t(Xf, torch::kBFloat16, "Xf");
+    TORCH_CHECK(Xf.dim() == 2 && Xf.size(0) % 128 == 0,
+                "m_pad must be a mult of 128");
+    const int64_t m_pad = Xf.size(0), fa = Xf.size(1);
+    TORCH_CHECK(fa >= 32 && fa % 32 == 0, "fa must be a multiple of 32");
+    check_t(WbfT, torch::kBFloat16, "WbfT");
+    TORCH_CHECK(WbfT.dim() == 2 && WbfT.size(1) == fa &&
+                WbfT.size(0) >= 128 && WbfT.size(0) % 128 == 0,
+                "WbfT must be [ncols_pad, fa], ncols_pad a mult of 128");
+    const int64_t ncols_pad = WbfT.size(0);
+    TORCH_CHECK(m_pad / 128 <= INT32_MAX && ncols_pad / 128 <= 65535,
+                "too many tiles for one launch");
+    check_vec(yf, torch::kFloat32, m_pad, "yf");
+    check_2d(cnt, torch::kInt32, 2, ncols_pad, "cnt");
+    if (m_pad == 0) return;
+    auto stream = c10::hip::getCurrentHIPStream().stream();
+    hipError_t err = skdist_score_counts(
+        Xf.data_ptr(), WbfT.data_ptr(), yf.data_ptr(), cnt.data_ptr(),
+        m_pad, (int)fa, (int)ncols_pad, (int)gk, stream);
+    TORCH_CHECK(err == hipSuccess, "score_fold_counts: ",
+                hipGetErrorString(err));
+}
+
 void standardize(torch::Tensor X, torch::Tensor mean,
                  torch::Tensor inv_std, torch::Tensor out, int64_t f) {
     check_t(out, torch::kBFloat16, "out");
@@ -1580,6 +1611,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "fused fold-scoring GEMM + per-column stats");
     m.def("score_fold_groups", &score_fold_groups,
           "fused multiclass fold scoring: per-group hits or log-loss");
+    m.def("score_fold_counts", &score_fold_counts,
+          "fused F1 fold scoring: per-column predicted and true-positive "
+          "counts");
     m.def("standardize", &standardize,
           "fused standardize + augment + bf16 cast");
     m.def("hash_vectorize", &hash_vectorize,

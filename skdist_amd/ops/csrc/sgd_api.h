@@ -65,6 +65,10 @@ hipError_t skdist_score_groups(
     const void* Xf, const void* WbfT, const void* yf, void* part,
     long long m_pad, int fa, int ncols_pad, int gk, int mode,
     hipStream_t stream);
+// gk: 1 (binary) or 3..128; cnt [2][ncols_pad] int32, zeroed by the caller
+hipError_t skdist_score_counts(
+    const void* Xf, const void* WbfT, const void* yf, void* cnt,
+    long long m_pad, int fa, int ncols_pad, int gk, hipStream_t stream);
 hipError_t skdist_standardize(
     const void* X, const void* mean, const void* inv_std, void* out,
     long long n, int f, int fa, hipStream_t stream);

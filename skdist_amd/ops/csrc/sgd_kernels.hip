@@ -1473,3 +1473,156 @@ extern "C" hipError_t skdist_score_groups(
                        (const float*)yf, (float*)part, fa, gk, mode);
     return hipGetLastError();
 }
+
+// ---------------------------------------------------------------------- //
+// K5c: fused F1 fold scoring -- k_score_groups' GEMM tile and z image with
+// an epilogue that counts, per column, the rows predicted as that column's
+// class and the ones of them that are right.  Per model and class F1 is a
+// function of tp, the predicted count and the support, and the support
+// does not depend on the model (the host takes it from the fold's y), so
+// neither the decision values nor a K x K confusion matrix reach HBM.
+// grid: (m_pad/128, ncols_pad/128), block 256.
+//
+// Xf, WbfT, yf and the column layout are k_score_groups'; gk == 1 is the
+// binary search, one column per model.  cnt [2][ncols_pad] int32, zeroed
+// by the caller; the kernel adds, for the column of group g and class c,
+//   gk >= 3: cnt[0][col] += #rows with argmax over the group == c, the
+//                           lowest class winning a tie (numpy.argmax)
+//            cnt[1][col] += #those rows with y == c
+//   gk == 1: cnt[0][col] += #rows with z >= 0
+//            cnt[1][col] += #rows with z >= 0 and y != 0    (k_score's sign)
+// A row with y < -1e29 (pad) adds nothing; a valid y is clamped into
+// 0..gk-1.  Dead columns stay 0, groups past the last model are counted
+// like any other and the host drops them.
+//
+// Epilogue: z goes through LDS as fp32, 64 rows at a time; a lane owns one
+// (row, group), wave w takes groups w, w + 4, ... in both halves.
+//   grouped: the lane walks its gk columns in ascending order and does one
+//            LDS integer add into pcS[g * gk + best], and one into tpS
+//            when best == y.  The 64 lanes of a wave spread over the gk
+//            counters of one group.
+//   binary:  all 64 lanes of a wave would hit one counter, so the sum over
+//            rows is two ballots + popcounts per column and lane i carries
+//            the two totals of column w + 4 * i over both halves; it
+//            stores them to pcS / tpS at the end.  No LDS atomics.
+// pcS / tpS are zeroed before the main loop and carried over both halves;
+// then thread t adds pcS[t] (t < 128) or tpS[t - 128] to its column of cnt
+// with one int32 atomicAdd, skipping zeros.  Integer adds are exact and
+// order-free, so the result does not depend on the launch order: the
+// determinism contract of the other scoring kernels.  k_score_groups keeps
+// it with plain stores into a per-row-tile `part` because its log-loss
+// sums are floats; counts need no such array, which per class would reach
+// hundreds of MB at 128 classes x 500 models.
+//
+// Built without packed fp32 instructions (NO_PK_F32).
+// __launch_bounds__(256, 4): 106 VGPRs, no AGPRs, no scratch, 34560 B of
+// LDS (the z image, y_s, pcS and tpS): 4 workgroups per CU.
+// ---------------------------------------------------------------------- //
+#define SCC_LDS (SMX_ZBYTES + 512 + 1024)  // z image, y_s, pcS + tpS
+static_assert(SCC_LDS <= WG4_LDS_MAX, "k_score_counts: 4 workgroups per CU");
+
+template <bool BINARY>
+static __device__ __forceinline__ void score_counts_epilogue(
+    const f32x4 (&acc)[4][4], float* zS, const float* y_s, int* pcS,
+    int* tpS, int gk, int lane, int w)
+{
+    const int wr = ((w >> 1) & 1) * 64;
+    const int wc = (w & 1) * 64;
+    const int fr = lane & 15;
+    const int rw = lane >> 4;
+    const int gpt = BN / gk;
+    int cpc = 0, ctp = 0;  // binary, lane i: totals of column w + 4 * i
+    for (int h = 0; h < 2; ++h) {
+        if (wr == h * 64) SPILL_Z_HALF(acc, zS, wc, fr, rw);
+        __syncthreads();
+        const float yv = y_s[h * 64 + lane];
+        const bool valid = !(yv < -1e29f);
+        const float* zrow = zS + lane * SMX_ZLD;
+        if (BINARY) {
+            const bool pos = valid && yv != 0.f;
+            for (int g = w, i = 0; g < BN; g += 4, ++i) {
+                const bool p = valid && zrow[g] >= 0.f;
+                const int npc = __popcll(__ballot(p));
+                const int ntp = __popcll(__ballot(p && pos));
+                if (lane == i) { cpc += npc; ctp += ntp; }
+            }
+        } else {
+            // the class index, kept inside the group whatever yf holds
+            const int yi = valid ? min(max((int)yv, 0), gk - 1) : 0;
+            for (int g = w; g < gpt; g += 4) {
+                const float* zr = zrow + g * gk;
+                float mx = zr[0];
+                int best = 0;
+                for (int c = 1; c < gk; ++c) {
+                    const float z = zr[c];
+                    if (z > mx) { mx = z; best = c; }  // ties keep the lowest
+                }
+                if (valid) {
+                    atomicAdd(&pcS[g * gk + best], 1);
+                    if (best == yi) atomicAdd(&tpS[g * gk + best], 1);
+                }
+            }
+        }
+        if (h == 0) __syncthreads();  // zS is rewritten for rows 64..127
+    }
+    if (BINARY && lane < BN / 4) {
+        pcS[w + 4 * lane] = cpc;
+        tpS[w + 4 * lane] = ctp;
+    }
+}
+
+extern "C" __global__ NO_PK_F32 __launch_bounds__(256, 4)
+void k_score_counts(
+    const __bf16* __restrict__ Xf,    // [m_pad][fa] gathered fold rows
+    const __bf16* __restrict__ WbfT,  // [ncols_pad][fa], group layout
+    const float* __restrict__ yf,     // [m_pad] class index (-1e30 pad)
+    int* __restrict__ cnt,            // [2][ncols_pad], the kernel adds
+    int fa, int ncols_pad, int gk)
+{
+    extern __shared__ __attribute__((aligned(16))) char sm[];
+    float* zS = (float*)sm;                     // [64][SMX_ZLD]
+    float* y_s = (float*)(sm + SMX_ZBYTES);     // [BM]
+    int* pcS = (int*)(sm + SMX_ZBYTES + 512);   // [BN] predicted as the class
+    int* tpS = pcS + BN;                        // [BN] ... and y is the class
+
+    const int tid = threadIdx.x;
+    const int bm = blockIdx.x * BM;
+    const int bn = blockIdx.y * BN;
+    const int lane = tid & 63;
+    const int w = tid >> 6;
+    if (tid < BM) y_s[tid] = yf[bm + tid];
+    pcS[tid] = 0;  // 256 threads: pcS and tpS, both past the GEMM buffers
+
+    f32x4 acc[4][4] = {};
+    gemm_tile_128(acc, sm, Xf + (long long)bm * fa,
+                    WbfT + (long long)bn * fa, fa, lane, w);
+    // every wave is done reading the GEMM buffers; y_s and the zeroed
+    // counters are visible
+    __syncthreads();
+
+    if (gk == 1)
+        score_counts_epilogue<true>(acc, zS, y_s, pcS, tpS, gk, lane, w);
+    else
+        score_counts_epilogue<false>(acc, zS, y_s, pcS, tpS, gk, lane, w);
+    __syncthreads();
+    // thread t < 128: pc of column t; t >= 128: tp of column t - 128
+    const int v = pcS[tid];
+    if (v != 0)
+        atomicAdd(cnt + (long long)(tid >> 7) * ncols_pad + bn + (tid & 127),
+                  v);
+}
+
+extern "C" hipError_t skdist_score_counts(
+    const void* Xf, const void* WbfT, const void* yf, void* cnt,
+    long long m_pad, int fa, int ncols_pad, int gk, hipStream_t stream)
+{
+    if ((gk != 1 && (gk < 3 || gk > BN)) || fa < BK || fa % BK != 0 ||
+        m_pad < 0 || m_pad % BM != 0 || ncols_pad < 0 || ncols_pad % BN != 0)
+        return hipErrorInvalidValue;
+    if (m_pad == 0 || ncols_pad == 0) return hipSuccess;
+    dim3 grid((unsigned)(m_pad / BM), ncols_pad / BN);
+    hipLaunchKernelGGL(k_score_counts, grid, dim3(256), SCC_LDS, stream,
+                       (const __bf16*)Xf, (const __bf16*)WbfT,
+                       (const float*)yf, (int*)cnt, fa, ncols_pad, gk);
+    return hipGetLastError();
+}

@@ -1,12 +1,20 @@
 """
-``batched_scores_by_fold`` of one multiclass search: the fused
-k_score_groups route against the ``_MetricState`` torch route (forced by
-patching ``_sgd._use_hip``), alternating in one process.  Prints one JSON
-line: per metric and route [median, min, max] ms of a host timer around the
-call (it ends in device-to-host copies), and the largest difference between
-the two routes' scores (the torch route rounds z to bf16).
+``batched_scores_by_fold`` of one multiclass search: the fused route
+(k_score_groups; k_score_counts for the F1 metrics) against the
+``_MetricState`` torch route (forced by patching ``_sgd._use_hip``),
+alternating in one process.  Prints one JSON line: per metric and route
+[median, min, max] ms of a host timer around the call (it ends in
+device-to-host copies), and the largest difference between the two routes'
+scores (the torch route rounds z to bf16).
 
     python tools/score_groups_bench.py [--rows 200000] [--candidates 300]
+
+The F1 figures of docs/BENCHMARKS.md, at the training set of
+examples/search/covtype_scale.py and at 1M rows x 500 models:
+
+    ... --metrics f1_weighted --features 54 --classes 7 \
+        --rows 464809 --candidates 4        (and --rows 1000000
+                                             --candidates 100)
 """
 
 import argparse
@@ -26,8 +34,11 @@ def main():
     ap.add_argument("--rows", type=int, default=200_000)
     ap.add_argument("--candidates", type=int, default=300)
     ap.add_argument("--repeats", type=int, default=6)
+    ap.add_argument("--features", type=int, default=64)
+    ap.add_argument("--classes", type=int, default=10)
+    ap.add_argument("--metrics", default="accuracy,neg_log_loss")
     a = ap.parse_args()
-    a.features, a.classes, a.folds, a.warmup = 64, 10, 5, 2
+    a.folds, a.warmup = 5, 2
     if not torch.cuda.is_available():
         sys.exit("score_groups_bench: needs a GPU (no CPU timing)")
 
@@ -53,7 +64,7 @@ def main():
     routes = {"fused": S._use_hip, "torch": lambda d: False}
     res = {"rows": n, "fa": int(ds.fa), "classes": K, "models": nm,
            "folds": a.folds}
-    for metric in ("accuracy", "neg_log_loss"):
+    for metric in a.metrics.split(","):
         t = {r: [] for r in routes}
         score = {}
         for rep in range(a.warmup + a.repeats):

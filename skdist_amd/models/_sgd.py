@@ -698,6 +698,9 @@ def batched_scores_by_fold(ds, W, model_folds, col_class, n_classes,
         and ds.classes_ is not None
         and 2 <= n_classes <= 128
     )
+    # exact binary roc_auc: z as the torch path forms it, ranked per column
+    # by k_auc_counts (auc_kernels.hip) where that is not the slower route
+    use_hip_auc = _use_hip(device) and metric == "roc_auc"
     for f in np.unique(model_folds[model_folds >= 0]):
         mids = np.flatnonzero(model_folds == f)
         cols_np = (mids[:, None] * cpm + np.arange(cpm)).ravel()
@@ -716,6 +719,16 @@ def batched_scores_by_fold(ds, W, model_folds, col_class, n_classes,
         if use_hip_counts:
             out[mids] = _score_fold_hip_counts(
                 ds, Wf, rows, n_classes, metric)
+            continue
+        if use_hip_auc and _auc_kernel_pays(len(rows), nm):
+            cls = np.unique(col_class[cols_np])
+            assert len(cls) == 1, "binary roc_auc: one class per fold"
+            zs = [(ds.Xaug.index_select(0, rows[lo: lo + chunk]) @ Wf).to(
+                torch.float32)
+                for lo in range(0, max(len(rows), 1), chunk)]
+            out[mids] = _score_fold_hip_auc(
+                zs[0] if len(zs) == 1 else torch.cat(zs),
+                ds.y_float.index_select(0, rows), cls[0])
             continue
         spec = _Shim()
         spec.col_class = torch.as_tensor(
@@ -859,6 +872,49 @@ def _score_fold_hip_counts(ds, Wf, rows, n_classes, metric):
         pc = torch.cat([m - pc1, pc1], dim=1)
         tp = torch.cat([(m - support[1]) - (pc1 - tp1), tp1], dim=1)
     return _f1_from_counts(tp, pc, support.expand(nm, k), metric)
+
+
+# k_auc_counts gives a column to one workgroup, so its time follows the
+# fold's rows whatever the number of columns, while the torch route's
+# sorts spread a few long columns over the whole device.  Measured
+# (docs/BENCHMARKS.md, "ROC AUC fold scoring"): the kernel is the faster
+# route from 64 models per fold at every fold size, and for any number of
+# models up to 25,000 rows per fold; a long fold with few models keeps the
+# torch route.
+_AUC_KERNEL_MIN_MODELS = 64
+_AUC_KERNEL_SHORT_FOLD = 25_000
+
+
+def _auc_kernel_pays(m, n_models):
+    return n_models >= _AUC_KERNEL_MIN_MODELS or m <= _AUC_KERNEL_SHORT_FOLD
+
+
+def _score_fold_hip_auc(Z, y_rows, cls):
+    """Exact tie-aware ROC AUC of one fold through k_auc_counts
+    (auc_kernels.hip).  ``Z`` [M, n_models] fp32 decision values of the
+    fold's rows, ``y_rows`` [M] their labels, ``cls`` the positive class.
+    The rows are partitioned negatives first (stable, on the device), one
+    ``index_select`` of the transposed view lays them out one row per
+    model, and the kernel sorts each model's negatives and counts, per
+    positive, the negatives below it and the negatives not above it.  That
+    integer ``U2`` is twice ``_MetricState``'s rank sum, so the float64
+    quotient equals what ``_MetricState.finalize`` returns for the same Z.
+    The kernel consumes ZT (it is one of the sort's two buffers).  Returns
+    np.ndarray [n_models]."""
+    from ..ops import require_hip
+
+    M, nm = Z.shape
+    pos = y_rows == float(cls)
+    neg_rows = torch.nonzero(~pos).flatten()
+    order = torch.cat([neg_rows, torch.nonzero(pos).flatten()])
+    n_neg = int(neg_rows.numel())
+    ZT = Z.t().index_select(1, order)           # [nm, M], contiguous
+    scratch = torch.empty(nm, n_neg, dtype=torch.int32, device=Z.device)
+    # zeros: an empty fold launches nothing
+    u2 = torch.zeros(nm, dtype=torch.int64, device=Z.device)
+    require_hip().auc_counts(ZT, n_neg, scratch, u2)
+    num = u2.cpu().numpy().astype(np.float64) * 0.5
+    return num / max(float(M - n_neg) * float(n_neg), 1.0)
 
 
 class _MetricState:

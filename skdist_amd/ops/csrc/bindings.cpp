@@ -1447,6 +1447,39 @@ void score_fold_counts(torch::Tensor Xf, torch::Tensor WbfT,
                 hipGetErrorString(err));
 }
 
+// exact ROC AUC counts of one fold: ZT [nm, M] f32, one row per model with
+// the n_neg negatives first; out [nm] int64 takes U2 = sum over positives
+// of (#negatives below) + (#negatives not above), auc = U2 / (2 P N).
+// ZT IS CONSUMED: the kernel's radix sort ping-pongs between scratch
+// [nm, n_neg] int32 and the negatives' part of ZT, which holds sorted keys
+// afterwards
+void auc_counts(torch::Tensor ZT, int64_t n_neg, torch::Tensor scratch,
+                torch::Tensor out) {
+    check_t(ZT, torch::kFloat32, "ZT");
+    TORCH_CHECK(ZT.dim() == 2, "ZT must be [nm, M]");
+    const int64_t nm = ZT.size(0), M = ZT.size(1);
+    TORCH_CHECK(M <= INT32_MAX && nm <= INT32_MAX,
+                "a fold must have fewer than 2^31 rows and models");
+    TORCH_CHECK(n_neg >= 0 && n_neg <= M, "n_neg must be in [0, M], got ",
+                n_neg);
+    if (n_neg == 0) {
+        check_t(scratch, torch::kInt32, "scratch");
+        TORCH_CHECK(scratch.numel() == 0,
+                    "scratch must be empty when n_neg is 0");
+    } else {
+        check_2d(scratch, torch::kInt32, nm, n_neg, "scratch");
+    }
+    check_t(out, torch::kInt64, "out");
+    TORCH_CHECK(out.dim() == 1 && out.size(0) == nm, "out must be [", nm,
+                "]");
+    if (nm == 0 || M == 0) return;
+    auto stream = c10::hip::getCurrentHIPStream().stream();
+    hipError_t err = skdist_auc_counts(
+        ZT.data_ptr(), scratch.data_ptr(), out.data_ptr(), nm, M, n_neg,
+        stream);
+    TORCH_CHECK(err == hipSuccess, "auc_counts: ", hipGetErrorString(err));
+}
+
 void standardize(torch::Tensor X, torch::Tensor mean,
                  torch::Tensor inv_std, torch::Tensor out, int64_t f) {
     check_t(out, torch::kBFloat16, "out");
@@ -1614,6 +1647,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("score_fold_counts", &score_fold_counts,
           "fused F1 fold scoring: per-column predicted and true-positive "
           "counts");
+    m.def("auc_counts", &auc_counts,
+          "exact ROC AUC counts per model: U2 = sum over positives of "
+          "(#negatives <) + (#negatives <=).  ZT [nm, M] f32 with the n_neg "
+          "negatives of each row first is CONSUMED: the sort ping-pongs "
+          "between scratch [nm, n_neg] int32 and the negatives' part of ZT",
+          pybind11::arg("ZT"), pybind11::arg("n_neg"),
+          pybind11::arg("scratch"), pybind11::arg("out"));
     m.def("standardize", &standardize,
           "fused standardize + augment + bf16 cast");
     m.def("hash_vectorize", &hash_vectorize,

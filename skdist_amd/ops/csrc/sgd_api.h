@@ -1,6 +1,6 @@
-// C launchers of the dense SGD family: included by sgd_kernels.hip, which
-// defines them, and by bindings.cpp, which calls them, so the compiler
-// checks each signature on both sides.
+// C launchers of the dense SGD family: included by sgd_kernels.hip and
+// auc_kernels.hip, which define them, and by bindings.cpp, which calls
+// them, so the compiler checks each signature on both sides.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -69,6 +69,13 @@ hipError_t skdist_score_groups(
 hipError_t skdist_score_counts(
     const void* Xf, const void* WbfT, const void* yf, void* cnt,
     long long m_pad, int fa, int ncols_pad, int gk, hipStream_t stream);
+// exact ROC AUC counts (auc_kernels.hip).  ZT [nm][M] f32, the n_neg
+// negatives of each row first; scratch [nm][n_neg] int32; out [nm] int64
+// U2.  ZT is consumed: the sort ping-pongs between scratch and the
+// negatives' part of ZT.  0 <= n_neg <= M < 2^31
+hipError_t skdist_auc_counts(
+    void* ZT, void* scratch, void* out, long long nm, long long M,
+    long long n_neg, hipStream_t stream);
 hipError_t skdist_standardize(
     const void* X, const void* mean, const void* inv_std, void* out,
     long long n, int f, int fa, hipStream_t stream);

@@ -42,8 +42,8 @@ import warnings
 import numpy as np
 import torch
 
-from ._sgd import (_LOSS_IDS, _MetricState, _auc_kernel_pays,
-                   _score_fold_hip_auc, _use_hip, encode_labels)
+from ._sgd import (_LOSS_IDS, _RANK_METRICS, _MetricState,
+                   _rank_kernel_route, _use_hip, encode_labels)
 
 LOSS_LOG, LOSS_HINGE, LOSS_SQUARED = 0, 1, 2
 
@@ -723,12 +723,13 @@ def sparse_scores_by_fold(ds, W, model_folds, col_class, n_classes,
         ssel = ones.expand(cp).contiguous()
         rows = torch.nonzero(ds.fold_id == int(fsel)).flatten()
         nm = len(mids)
-        if (hip and metric == "roc_auc"
-                and _auc_kernel_pays(len(rows), nm)):
+        rank_kernel = (_rank_kernel_route(metric, len(rows), nm)
+                       if hip and metric in _RANK_METRICS else None)
+        if rank_kernel is not None:
             # the fold's whole Z, as the torch path collects it, ranked per
-            # column by k_auc_counts
+            # column by k_auc_counts / k_ap_sums
             cls = np.unique(col_class[cols_np])
-            assert len(cls) == 1, "binary roc_auc: one class per fold"
+            assert len(cls) == 1, f"binary {metric}: one class per fold"
             zs = []
             for lo in range(0, max(len(rows), 1), chunk):
                 r = rows[lo: lo + chunk].to(torch.int64).contiguous()
@@ -738,7 +739,7 @@ def sparse_scores_by_fold(ds, W, model_folds, col_class, n_classes,
                                    ssel, r, Z)
                 zs.append(Z)
             Z = zs[0] if len(zs) == 1 else torch.cat(zs)
-            out[mids] = _score_fold_hip_auc(
+            out[mids] = rank_kernel(
                 Z[:, :nsel], ds.y_float.index_select(0, rows), cls[0])
             continue
         spec = _Shim()

@@ -65,7 +65,7 @@ def _make_dataset(X, y, cluster=None, device=None, standardize=True,
 
 _DEVICE_METRICS = {
     "accuracy", "f1", "f1_weighted", "f1_macro", "neg_log_loss", "roc_auc",
-    "r2", "neg_mean_squared_error",
+    "average_precision", "r2", "neg_mean_squared_error",
 }
 
 
@@ -357,6 +357,10 @@ class _BatchedLinearBase(BaseEstimator):
                 raise FallbackToGeneric(
                     "multiclass roc_auc needs sklearn's multi_class "
                     "semantics: generic path")
+            if metric == "average_precision" and k > 2:
+                raise FallbackToGeneric(
+                    "average_precision is binary only (sklearn's scorer "
+                    "rejects multiclass): generic path")
         else:
             n_classes = 2
             cols_per_model = 1
@@ -531,6 +535,10 @@ class _BatchedLinearBase(BaseEstimator):
                 raise FallbackToGeneric(
                     "multiclass roc_auc needs sklearn's multi_class "
                     "semantics: generic path")
+            if metric == "average_precision" and k > 2:
+                raise FallbackToGeneric(
+                    "average_precision is binary only (sklearn's scorer "
+                    "rejects multiclass): generic path")
         else:
             n_classes = 2
             cls = np.array([-1], dtype=np.int32)

@@ -46,6 +46,10 @@
 //           (U2 passes 2^32 at 40,000 x 40,000 rows).  Lanes combine
 //           through LDS in a fixed tree, lane 0 stores.
 //
+// k_ap_sums (average precision, described above the kernel) shares the key,
+// the histograms and the passes, sorts both halves of the row and searches
+// both.
+//
 // n_neg == 0 or P == 0 gives U2 = 0 and touches neither ZT nor scratch.
 // Indices are 32-bit inside a column (M < 2^31, checked by the launcher);
 // the column's base address is 64-bit.
@@ -122,35 +126,19 @@ static __device__ __forceinline__ void auc_radix_pass(
     __syncthreads();
 }
 
-// 30 VGPRs, 0 AGPRs, no scratch, 14336 B of LDS (gfx950, -O3): 8 waves per
-// SIMD by registers, 8 workgroups per CU
-extern "C" __global__ __launch_bounds__(256)
-void k_auc_counts(
-    float* ZT,            // [nm][M], negatives first; consumed
-    int* scratch,         // [nm][n_neg]
-    long long* out,       // [nm] U2
-    unsigned M, unsigned n_neg)
+// The whole sort of one segment: A[0..n) decision values become their keys
+// in ascending order, in place; B[0..n) is the other buffer of the
+// ping-pong (A -> B -> A -> B -> A).  hist [4][256] is cleared and used
+// here; wcnt is all zero on entry and on return.  Every lane of the
+// workgroup calls it, behind a barrier after the last use of hist, A and B;
+// n == 0 does nothing.
+static __device__ __forceinline__ void auc_sort_keys(
+    unsigned* A, unsigned* B, unsigned n, int* hist, int* wcnt, int tid)
 {
-    __shared__ int hist[4 * 256];            // digit counts, then offsets
-    __shared__ int wcnt[2 * AUC_WCNT];       // [buf][wave][digit]
-    __shared__ unsigned long long red[256];
-
-    const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int w = tid >> 6;
-    const unsigned n = n_neg;
-    const unsigned P = M - n_neg;
-    if (n == 0u || P == 0u) {
-        if (tid == 0) out[blockIdx.x] = 0;
-        return;
-    }
-    unsigned* A = (unsigned*)(ZT + (size_t)blockIdx.x * M);
-    unsigned* B = (unsigned*)(scratch + (size_t)blockIdx.x * n);
-
 #pragma unroll
     for (int v = 0; v < 4; ++v) hist[v * 256 + tid] = 0;
-#pragma unroll
-    for (int v = 0; v < 8; ++v) wcnt[v * 256 + tid] = 0;
     __syncthreads();
 
     // all four digit histograms in one sweep
@@ -184,6 +172,34 @@ void k_auc_counts(
     auc_radix_pass<false>(B, A, n, 8, hist + 256, wcnt, tid);
     auc_radix_pass<false>(A, B, n, 16, hist + 512, wcnt, tid);
     auc_radix_pass<false>(B, A, n, 24, hist + 768, wcnt, tid);
+}
+
+// 30 VGPRs, 0 AGPRs, no scratch, 14336 B of LDS (gfx950, -O3): 8 waves per
+// SIMD by registers, 8 workgroups per CU
+extern "C" __global__ __launch_bounds__(256)
+void k_auc_counts(
+    float* ZT,            // [nm][M], negatives first; consumed
+    int* scratch,         // [nm][n_neg]
+    long long* out,       // [nm] U2
+    unsigned M, unsigned n_neg)
+{
+    __shared__ int hist[4 * 256];            // digit counts, then offsets
+    __shared__ int wcnt[2 * AUC_WCNT];       // [buf][wave][digit]
+    __shared__ unsigned long long red[256];
+
+    const int tid = threadIdx.x;
+    const unsigned n = n_neg;
+    const unsigned P = M - n_neg;
+    if (n == 0u || P == 0u) {
+        if (tid == 0) out[blockIdx.x] = 0;
+        return;
+    }
+    unsigned* A = (unsigned*)(ZT + (size_t)blockIdx.x * M);
+    unsigned* B = (unsigned*)(scratch + (size_t)blockIdx.x * n);
+
+#pragma unroll
+    for (int v = 0; v < 8; ++v) wcnt[v * 256 + tid] = 0;
+    auc_sort_keys(A, B, n, hist, wcnt, tid);
 
     // A[0..n): the negatives' keys, ascending; A[n..M): the positives' z
     const unsigned* keys = A;
@@ -229,6 +245,101 @@ void k_auc_counts(
     if (tid == 0) out[blockIdx.x] = (long long)red[0];
 }
 
+// Average precision of one fold, per model:
+//   S[c] = sum over positives i of TP(i) / (TP(i) + FP(i)),  AP = S / P
+//   TP(i) = #positives with z >= z_i, FP(i) = #negatives with z >= z_i
+// (sklearn's step-wise average_precision_score: thresholds at the distinct
+// values, ties grouped).  ZT [nm][M] as above, scratch [nm][M], out [nm]
+// fp64.  Both halves of the row are sorted with auc_sort_keys, each
+// between its own part of ZT and the same part of scratch, so all of ZT is
+// consumed.  A lane then takes SORTED positives strided by 256, AUC_ILP at
+// a time (neighbouring lanes hold neighbouring keys, so their probes land
+// close together), and runs one lower-bound search over the negatives' keys
+// and one over the positives' keys in a single loop: a segment's half
+// length is 0 once its search is down to one candidate, and no probe is
+// issued for it, so every probe index stays inside its own segment:
+//   TP = P - lower_bound_pos(k),  FP = n - lower_bound_neg(k)
+// The ratio is one correctly rounded fp64 division of exact integers; a
+// lane adds its ratios in ascending index, the lanes combine in the fixed
+// LDS tree and lane 0 stores, so S does not depend on the launch order.
+// P == 0 stores 0.0 and touches no memory; n == 0 sorts the positives
+// alone and gives S = P exactly.
+//
+// 30 VGPRs, 0 AGPRs, no scratch, 14336 B of LDS (gfx950, -O3): 8 waves per
+// SIMD by registers, 8 workgroups per CU
+extern "C" __global__ __launch_bounds__(256)
+void k_ap_sums(
+    float* ZT,            // [nm][M], negatives first; consumed
+    int* scratch,         // [nm][M]
+    double* out,          // [nm] S
+    unsigned M, unsigned n_neg)
+{
+    __shared__ int hist[4 * 256];            // digit counts, then offsets
+    __shared__ int wcnt[2 * AUC_WCNT];       // [buf][wave][digit]
+    __shared__ double red[256];
+
+    const int tid = threadIdx.x;
+    const unsigned n = n_neg;
+    const unsigned P = M - n_neg;
+    if (P == 0u) {
+        if (tid == 0) out[blockIdx.x] = 0.0;
+        return;
+    }
+    unsigned* A = (unsigned*)(ZT + (size_t)blockIdx.x * M);
+    unsigned* B = (unsigned*)(scratch + (size_t)blockIdx.x * M);
+
+#pragma unroll
+    for (int v = 0; v < 8; ++v) wcnt[v * 256 + tid] = 0;
+    auc_sort_keys(A, B, n, hist, wcnt, tid);
+    auc_sort_keys(A + n, B + n, P, hist, wcnt, tid);
+
+    // ascending keys: the negatives' in A[0..n), the positives' in A[n..M)
+    const unsigned* nk = A;
+    const unsigned* pk = A + n;
+    double acc = 0.0;
+    for (unsigned j0 = 0; j0 < P; j0 += AUC_TILE * AUC_ILP) {
+        unsigned kp[AUC_ILP], ln[AUC_ILP], lp[AUC_ILP];
+        bool ok[AUC_ILP];
+#pragma unroll
+        for (int u = 0; u < AUC_ILP; ++u) {
+            const unsigned j = j0 + u * AUC_TILE + tid;
+            ok[u] = j < P;
+            kp[u] = ok[u] ? pk[j] : 0u;
+            ln[u] = lp[u] = 0u;
+        }
+        // ln / lp: first negative / positive key >= kp.  An answer stays in
+        // [l, l + len] with l + len <= the segment's length, so
+        // l + half - 1 is inside the segment whenever half >= 1
+        unsigned lenn = n, lenp = P;
+        while (lenn > 1u || lenp > 1u) {
+            const unsigned hn = lenn >> 1, hp = lenp >> 1;
+#pragma unroll
+            for (int u = 0; u < AUC_ILP; ++u) {
+                if (hn) ln[u] += nk[ln[u] + hn - 1u] < kp[u] ? hn : 0u;
+                if (hp) lp[u] += pk[lp[u] + hp - 1u] < kp[u] ? hp : 0u;
+            }
+            lenn -= hn;
+            lenp -= hp;
+        }
+#pragma unroll
+        for (int u = 0; u < AUC_ILP; ++u) {
+            // ln <= n - 1 when n >= 1, lp <= P - 1
+            if (n) ln[u] += nk[ln[u]] < kp[u] ? 1u : 0u;
+            lp[u] += pk[lp[u]] < kp[u] ? 1u : 0u;
+            const unsigned tp = P - lp[u];
+            const unsigned fp = n - ln[u];
+            if (ok[u]) acc += (double)tp / (double)(tp + fp);
+        }
+    }
+    red[tid] = acc;
+    __syncthreads();
+    for (int s = 128; s > 0; s >>= 1) {
+        if (tid < s) red[tid] += red[tid + s];
+        __syncthreads();
+    }
+    if (tid == 0) out[blockIdx.x] = red[0];
+}
+
 extern "C" hipError_t skdist_auc_counts(
     void* ZT, void* scratch, void* out, long long nm, long long M,
     long long n_neg, hipStream_t stream)
@@ -239,6 +350,20 @@ extern "C" hipError_t skdist_auc_counts(
     if (nm == 0 || M == 0) return hipSuccess;
     hipLaunchKernelGGL(k_auc_counts, dim3((unsigned)nm), dim3(256), 0, stream,
                        (float*)ZT, (int*)scratch, (long long*)out,
+                       (unsigned)M, (unsigned)n_neg);
+    return hipGetLastError();
+}
+
+extern "C" hipError_t skdist_ap_sums(
+    void* ZT, void* scratch, void* out, long long nm, long long M,
+    long long n_neg, hipStream_t stream)
+{
+    if (nm < 0 || nm > 0x7fffffffLL || M < 0 || M > 0x7fffffffLL ||
+        n_neg < 0 || n_neg > M)
+        return hipErrorInvalidValue;
+    if (nm == 0 || M == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ap_sums, dim3((unsigned)nm), dim3(256), 0, stream,
+                       (float*)ZT, (int*)scratch, (double*)out,
                        (unsigned)M, (unsigned)n_neg);
     return hipGetLastError();
 }

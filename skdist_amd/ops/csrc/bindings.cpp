@@ -1480,6 +1480,32 @@ void auc_counts(torch::Tensor ZT, int64_t n_neg, torch::Tensor scratch,
     TORCH_CHECK(err == hipSuccess, "auc_counts: ", hipGetErrorString(err));
 }
 
+// average precision sums of one fold: ZT [nm, M] f32 as for auc_counts;
+// out [nm] float64 takes S = sum over positives of TP / (TP + FP) at the
+// positive's own threshold (ties grouped), AP = S / P.  ALL OF ZT IS
+// CONSUMED: both halves of a row are sorted, each between its own part of
+// ZT and of scratch [nm, M] int32
+void ap_sums(torch::Tensor ZT, int64_t n_neg, torch::Tensor scratch,
+             torch::Tensor out) {
+    check_t(ZT, torch::kFloat32, "ZT");
+    TORCH_CHECK(ZT.dim() == 2, "ZT must be [nm, M]");
+    const int64_t nm = ZT.size(0), M = ZT.size(1);
+    TORCH_CHECK(M <= INT32_MAX && nm <= INT32_MAX,
+                "a fold must have fewer than 2^31 rows and models");
+    TORCH_CHECK(n_neg >= 0 && n_neg <= M, "n_neg must be in [0, M], got ",
+                n_neg);
+    check_2d(scratch, torch::kInt32, nm, M, "scratch");
+    check_t(out, torch::kFloat64, "out");
+    TORCH_CHECK(out.dim() == 1 && out.size(0) == nm, "out must be [", nm,
+                "]");
+    if (nm == 0 || M == 0) return;
+    auto stream = c10::hip::getCurrentHIPStream().stream();
+    hipError_t err = skdist_ap_sums(
+        ZT.data_ptr(), scratch.data_ptr(), out.data_ptr(), nm, M, n_neg,
+        stream);
+    TORCH_CHECK(err == hipSuccess, "ap_sums: ", hipGetErrorString(err));
+}
+
 void standardize(torch::Tensor X, torch::Tensor mean,
                  torch::Tensor inv_std, torch::Tensor out, int64_t f) {
     check_t(out, torch::kBFloat16, "out");
@@ -1652,6 +1678,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           "(#negatives <) + (#negatives <=).  ZT [nm, M] f32 with the n_neg "
           "negatives of each row first is CONSUMED: the sort ping-pongs "
           "between scratch [nm, n_neg] int32 and the negatives' part of ZT",
+          pybind11::arg("ZT"), pybind11::arg("n_neg"),
+          pybind11::arg("scratch"), pybind11::arg("out"));
+    m.def("ap_sums", &ap_sums,
+          "average precision sums per model: S = sum over positives of "
+          "TP / (TP + FP), AP = S / P.  ZT [nm, M] f32 with the n_neg "
+          "negatives of each row first is CONSUMED: both halves are sorted "
+          "between ZT and scratch [nm, M] int32; out [nm] float64",
           pybind11::arg("ZT"), pybind11::arg("n_neg"),
           pybind11::arg("scratch"), pybind11::arg("out"));
     m.def("standardize", &standardize,

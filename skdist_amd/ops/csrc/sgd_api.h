@@ -76,6 +76,13 @@ hipError_t skdist_score_counts(
 hipError_t skdist_auc_counts(
     void* ZT, void* scratch, void* out, long long nm, long long M,
     long long n_neg, hipStream_t stream);
+// average precision sums (auc_kernels.hip).  ZT as above; scratch [nm][M]
+// int32; out [nm] f64 S = sum over positives of TP / (TP + FP), AP = S / P.
+// All of ZT is consumed: both halves are sorted, each between its own part
+// of ZT and of scratch.  0 <= n_neg <= M < 2^31
+hipError_t skdist_ap_sums(
+    void* ZT, void* scratch, void* out, long long nm, long long M,
+    long long n_neg, hipStream_t stream);
 hipError_t skdist_standardize(
     const void* X, const void* mean, const void* inv_std, void* out,
     long long n, int f, int fa, hipStream_t stream);
